@@ -1,9 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: Pearson correlation field, 256^3 grid x 64 ensemble members (BASELINE.json
-configs[1]), reported as whole-job Mvoxel-corr/s with the per-voxel kernel priced against the HBM roofline and the
-CPU calculator timed beside it.
+configs[1]), reported as whole-job Mvoxel-corr/s.  With --full the per-voxel kernel is also priced against the HBM
+roofline and the CPU calculator is timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, spins up and warms up, times exactly K steps (one block), writes the outputs if asked and prints the
+result line; nothing else.  --full adds what the headline figure does not need: the roofline of the dominant kernel
+(HIP-event kernel times in the timed blocks, committed PMC traffic), the CPU baseline with its parity check, the
+host-boundary timings, the N > 1 latency mode, and --repeats 5 by default.
+--dump-outputs DIR: after the timed steps, DIR/field.npy holds the float32 field the last timed step computed (whole
+grid, z-major, shape [zs, ys, xs], up to DUMP_FULL_MAX_VOXELS voxels; larger grids: the values at a fixed, seeded sample
+of DUMP_SAMPLE_VOXELS voxel indices, see dump_indices()).  Inputs depend only on the arguments, so two builds can be
+compared output for output.
 
 N > 1 launches its own ranks: the parent process (which never touches a GPU) starts
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...
@@ -21,8 +30,8 @@ Total work is fixed, so scaling is "strong".  Two modes are measured and both re
               ahead of the kernels that consume them (bulk evaluation of known points)
   latency     lookahead 0: every step is exchange -> reference-side preparation -> per-voxel kernel, in that order on the
               device (an interactively moved reference point: the next point is not known in advance)
-`value` is the throughput mode; `latency` carries the other.  The K timed steps are repeated --repeats times (each
-block fenced by barrier + synchronize on both sides, MAX over ranks); `value`/`ms_per_step` are the median block.
+`value` is the throughput mode; `latency` (--full) carries the other.  The K timed steps are repeated --repeats times
+(each block fenced by barrier + synchronize on both sides, MAX over ranks); `value`/`ms_per_step` are the median block.
 """
 import argparse
 import hashlib
@@ -37,7 +46,9 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_FULL_MAX_VOXELS = 1 << 23  # --dump-outputs writes the whole field up to 32 MiB of float32 ...
+DUMP_SAMPLE_VOXELS = 1 << 22    # ... and a fixed sample of 4 Mi voxels (16 MiB) of a larger one
 
 
 def parse():
@@ -45,7 +56,8 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps, median reported (default 1; 5 with --full)")
     ap.add_argument("--grid", type=int, nargs=3, default=[256, 256, 256], metavar=("XS", "YS", "ZS"))
     ap.add_argument("--members", type=int, default=64)
     ap.add_argument("--measure", default="pearson")
@@ -56,8 +68,16 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-boundary", action="store_true")
     ap.add_argument("--cpu-slices", type=int, default=0, help="z-slices of the CPU-baseline sample (0 = auto)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, CPU baseline + parity, host boundary, "
+                         "the N > 1 latency mode (and 5 timed blocks by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the field of the last timed step to DIR/field.npy (float32)")
     ap.add_argument("--cpu-baseline-child", default="", help=argparse.SUPPRESS)  # internal: see cpu_baseline_bound()
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def free_port():
@@ -224,7 +244,7 @@ def main():
         the MAX over ranks.  Returns ([ms_per_step per block], host issue ms per step, kernel ms average, launches)."""
         blocks, issue = [], []
         kernel_ms_sum, launches = 0.0, 0
-        eng.set_profiling(True)
+        eng.set_profiling(args.full)  # HIP events around every launch: only the roofline (--full) reads them
         for _ in range(repeats):
             run(0, args.warmup, lookahead)
             fence()
@@ -259,9 +279,11 @@ def main():
     stats = summarize(blocks)
     ms_per_step = stats["median"]
     value = n_total / (ms_per_step * 1e-3) / 1e6
+    if args.dump_outputs:  # before anything else writes `out`
+        dump_field(args, out, sharded, rank, world, multi, "cuda" if backend == "nccl" else "cpu")
 
-    latency = None
-    if multi:
+    latency = roofline = None
+    if multi and args.full:
         lblocks, lissue, lkernel, _ = timed_blocks(0, max(min(args.repeats, 3), 1))
         ls = summarize(lblocks)
         latency = {"lookahead": 0, "ms_per_step": ls["median"], "ms_per_step_min": ls["min"], "ms_per_step_max": ls["max"],
@@ -269,17 +291,18 @@ def main():
                    "host_issue_ms_per_step": round(lissue, 4), "kernel_ms": round(lkernel, 4),
                    "path": "per step: owner gathers cs floats -> broadcast -> reference-side preparation -> per-voxel kernel"}
 
-    # roofline of the dominant kernel: algorithmic bytes per launch = voxels per launch x (4*cs + 4)   
-    bytes_per_launch = n_local * (4 * cs + 4)
-    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-    traffic, traffic_stale = load_pmc_traffic(args, world)
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_stale": traffic_stale,
-                "kernel": kernel_name, "kernel_ms": round(kernel_ms, 4), "bytes_per_launch": bytes_per_launch,
-                "launches_timed": launches}
+    if args.full:
+        # roofline of the dominant kernel: algorithmic bytes per launch = voxels per launch x (4*cs + 4)   
+        bytes_per_launch = n_local * (4 * cs + 4)
+        achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+        traffic, traffic_stale = load_pmc_traffic(args, world)
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_stale": traffic_stale,
+                    "kernel": kernel_name, "kernel_ms": round(kernel_ms, 4), "bytes_per_launch": bytes_per_launch,
+                    "launches_timed": launches}
 
     cpu = parity = host_boundary = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:
             cpu, parity = cpu_baseline(args, eng, members, out, measure, pts[args.warmup + args.steps - 1], kwargs)
         if not args.no_host_boundary and not force_exchange:
@@ -289,7 +312,7 @@ def main():
         exchange = ("RCCL" if backend == "nccl" else backend + " (REHEARSAL: ranks share a GPU)") if multi else None
         line = {
             "metric": "Mvoxel-corr/s", "value": round(value, 1), "unit": "Mvoxel-corr/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "spinup_ms": args.spinup_ms,
+            "steps": args.steps, "warmup": args.warmup, "spinup_ms": args.spinup_ms, "full": args.full,
             "ms_per_step": ms_per_step, "ms_per_step_min": stats["min"], "ms_per_step_max": stats["max"],
             "timed_blocks": stats["blocks"], "host_issue_ms_per_step": round(issue_ms, 4),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -313,6 +336,45 @@ def main():
     eng.close()
     if multi:
         dist.destroy_process_group()
+
+
+def dump_indices(n_total, seed):
+    """Global voxel indices (z-major, x fastest) whose values --dump-outputs writes: None (every voxel) up to
+    DUMP_FULL_MAX_VOXELS, else one index drawn with `seed` from each of DUMP_SAMPLE_VOXELS equal strata of the grid
+    (sorted, distinct, the same for the same grid and seed)."""
+    import numpy as np
+    if n_total <= DUMP_FULL_MAX_VOXELS:
+        return None
+    s = np.arange(DUMP_SAMPLE_VOXELS + 1, dtype=np.int64) * n_total // DUMP_SAMPLE_VOXELS
+    return np.random.default_rng(seed).integers(s[:-1], s[1:])
+
+
+def dump_field(args, out, sharded, rank, world, multi, comm_device):
+    """--dump-outputs: the field the last timed step left in `out`, written by rank 0 as DIR/field.npy (float32).
+    N > 1: every rank contributes the sampled voxels of its own slab (all-gather of values and ownership masks)."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    xs, ys, zs = args.grid
+    idx = dump_indices(xs * ys * zs, args.seed)
+    gidx = torch.arange(xs * ys * zs, dtype=torch.int64) if idx is None else torch.from_numpy(idx)
+    lo = sharded.z_begin * xs * ys
+    mine = (gidx >= lo) & (gidx < lo + sharded.z_count * xs * ys)
+    vals = torch.zeros(gidx.numel(), dtype=torch.float32)
+    vals[mine] = out[(gidx[mine] - lo).to(out.device)].cpu()
+    if multi:
+        parts = [torch.empty(vals.numel(), dtype=torch.float32, device=comm_device) for _ in range(world)]
+        masks = [torch.empty(vals.numel(), dtype=torch.uint8, device=comm_device) for _ in range(world)]
+        dist.all_gather(parts, vals.to(comm_device))
+        dist.all_gather(masks, mine.to(torch.uint8).to(comm_device))
+        for v, m in zip(parts, masks):
+            m = m.cpu().bool()
+            vals[m] = v.cpu()[m]
+    if rank == 0:
+        d = Path(args.dump_outputs)
+        d.mkdir(parents=True, exist_ok=True)
+        field = vals.numpy()
+        np.save(d / "field.npy", field.reshape(zs, ys, xs) if idx is None else field)
 
 
 KERNEL_SOURCES = {  # translation units (and what they include) that decide the dominant kernel's HBM traffic

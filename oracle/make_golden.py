@@ -123,6 +123,24 @@ def main():
               pearson__reference=np.float32(ref.pearson(x, y)), ranks_y__reference=ref.ranks(y))
     np.savez_compressed(OUT / "known_answers.npz", **ka)
     print("known_answers:", {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in ka.items() if "__" in k})
+    record_reference_calls(ref, oracle)
+
+
+def record_reference_calls(ref, oracle):
+    """tests/golden/reference/calls.npz: the reference's answers to every call the oracle-vs-reference tests make
+    (test_oracle_vs_ref.py, test_pair_requests.py), keyed by the call's exact inputs -- those tests run against them
+    where oracle/_ref cannot be built."""
+    import test_oracle_vs_ref as t
+    import test_pair_requests as tp
+    rec = oracle_lib.RecordedReference(live=ref)
+    for cs in t.FIELD_MEMBER_COUNTS:
+        t.test_fields_bit_exact(oracle, rec, cs)
+    t.test_primitives_bit_exact(oracle, rec)
+    t.test_kendall_tau_a_cross_check(oracle, rec)
+    for cs in tp.PAIR_MEMBER_COUNTS:
+        tp.test_oracle_pairs_vs_reference_primitives(oracle, rec, cs)
+    rec.save(oracle_lib.RECORDED_CALLS)
+    print(f"reference_calls: {len(rec.calls)} calls -> {oracle_lib.RECORDED_CALLS.stat().st_size} bytes")
 
 
 if __name__ == "__main__":

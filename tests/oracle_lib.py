@@ -1,10 +1,13 @@
 """ctypes access to the CHECKER libraries (test infrastructure only):
    oracle/liboracle.so        this repo's CPU restatement (built on demand with g++; travels to the GPU box prebuilt)
    oracle/_ref/libref_corr.so the reference's own Correlation.cpp behind oracle/ref_driver.cpp (build container only)
+   tests/golden/reference/calls.npz  that object code's answers to the calls of the oracle-vs-reference tests, recorded
+                              by oracle/make_golden.py: what those tests compare against where oracle/_ref is absent
 Nothing under correrender_amd/ imports this module."""
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import subprocess
 from pathlib import Path
 
@@ -12,6 +15,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 ORACLE_DIR = ROOT / "oracle"
+RECORDED_CALLS = ROOT / "tests" / "golden" / "reference" / "calls.npz"
 FP = C.POINTER(C.c_float)
 
 PEARSON, SPEARMAN, KENDALL, MI_BINNED, MI_KRASKOV, BINNED_MI_CC, KMI_CC = range(7)
@@ -309,3 +313,87 @@ def reference_available() -> bool:
 
 def load_reference() -> Reference:
     return Reference(C.CDLL(str(ORACLE_DIR / "_ref" / "libref_corr.so")))
+
+
+def _call_key(*parts) -> str:
+    """sha256 of a call: method name, integer arguments and the exact bytes / dtype / shape of every array argument."""
+    h = hashlib.sha256()
+    for p in parts:
+        if isinstance(p, np.ndarray):
+            h.update(f"a{p.dtype.str}{p.shape}".encode())
+            h.update(np.ascontiguousarray(p).tobytes())
+        else:
+            h.update(f"v{p!r}".encode())
+    return h.hexdigest()
+
+
+class RecordedReference:
+    """The Reference interface answered from recorded calls of the reference's object code.  With `live` set, every
+    call is forwarded to it and recorded (oracle/make_golden.py); without, a call whose inputs were not recorded fails
+    instead of answering."""
+
+    def __init__(self, calls=None, live: Reference | None = None):
+        self.calls = dict(calls or {})
+        self.live = live
+
+    @classmethod
+    def load(cls, path=RECORDED_CALLS):
+        d = np.load(path, allow_pickle=False)
+        keys, offsets, values, scalar = d["keys"], d["offsets"], d["values"], d["scalar"]
+        calls = {}
+        for i, k in enumerate(keys):
+            v = values[offsets[i]:offsets[i + 1]]
+            calls[str(k)] = float(v[0]) if scalar[i] else v
+        return cls(calls)
+
+    def save(self, path=RECORDED_CALLS):
+        keys = sorted(self.calls)
+        vals = [np.atleast_1d(np.asarray(self.calls[k], np.float32)) for k in keys]
+        offsets = np.concatenate([[0], np.cumsum([v.size for v in vals])]).astype(np.int64)
+        np.savez_compressed(path, keys=np.array(keys), offsets=offsets, values=np.concatenate(vals),
+                            scalar=np.array([not isinstance(self.calls[k], np.ndarray) for k in keys]))
+
+    def _answer(self, compute, *parts):
+        key = _call_key(*parts)
+        if self.live is not None:
+            v = compute(self.live)
+            self.calls[key] = np.float32(v) if isinstance(v, float) else np.array(v, np.float32)
+            return v
+        if key not in self.calls:
+            raise KeyError(f"{parts[0]}: no recorded answer of the reference for these inputs "
+                           f"({RECORDED_CALLS.name}; oracle/make_golden.py re-records it where the reference is present)")
+        v = self.calls[key]
+        return float(v) if not isinstance(v, np.ndarray) else v.copy()
+
+    def pearson(self, x, y):
+        x, y = _f32(x), _f32(y)
+        return self._answer(lambda r: r.pearson(x, y), "pearson", x, y)
+
+    def ranks(self, v):
+        v = _f32(v)
+        return self._answer(lambda r: r.ranks(v), "ranks", v)
+
+    def kendall(self, x, y):
+        x, y = _f32(x), _f32(y)
+        return self._answer(lambda r: r.kendall(x, y), "kendall", x, y)
+
+    def kendall_slow(self, x, y):
+        x, y = _f32(x), _f32(y)
+        return self._answer(lambda r: r.kendall_slow(x, y), "kendall_slow", x, y)
+
+    def field(self, measure, members, ref_values, voxel_range=None):
+        members, ref_values = _members(members), _f32(ref_values)
+        return self._answer(lambda r: r.field(measure, members, ref_values, voxel_range), "field", int(measure),
+                            *members, ref_values, voxel_range)
+
+    def pair_requests(self, measure, members, idx_i, idx_j):
+        members = _members(members)
+        ii = np.ascontiguousarray(idx_i, dtype=np.uint64)
+        jj = np.ascontiguousarray(idx_j, dtype=np.uint64)
+        return self._answer(lambda r: r.pair_requests(measure, members, ii, jj), "pair_requests", int(measure),
+                            *members, ii, jj)
+
+
+def load_reference_or_recorded():
+    """The reference's object code where oracle/_ref was built, else its recorded answers."""
+    return load_reference() if reference_available() else RecordedReference.load()

@@ -1,5 +1,6 @@
 """Pair-request mode: the estimator between two arbitrary voxels per request.
-CPU: the oracle's pair evaluation vs the reference's own primitives (oracle/_ref) and the golden vectors.
+CPU: the oracle's pair evaluation vs the reference's own primitives (oracle/_ref, or their recorded answers where it is
+absent) and the golden vectors.
 GPU: crf_compute_requests vs the oracle."""
 from pathlib import Path
 
@@ -30,10 +31,16 @@ def _case(cs, seed, n=400, grid=(12, 10, 6)):
     return ens, pairs, idx(pairs[:, 0:3]), idx(pairs[:, 3:6])
 
 
-@pytest.mark.skipif(not oracle_lib.reference_available(), reason="oracle/_ref not built")
-@pytest.mark.parametrize("cs", [2, 16, 64, 100])
-def test_oracle_pairs_vs_reference_primitives(oracle, cs):
-    ref = oracle_lib.load_reference()
+PAIR_MEMBER_COUNTS = [2, 16, 64, 100]
+
+
+@pytest.fixture(scope="module")
+def ref():
+    return oracle_lib.load_reference_or_recorded()
+
+
+@pytest.mark.parametrize("cs", PAIR_MEMBER_COUNTS)
+def test_oracle_pairs_vs_reference_primitives(oracle, ref, cs):
     ens, _, ii, jj = _case(cs, 900 + cs)
     for m in (0, 1, 2):
         assert_bit_exact(oracle.pair_requests(m, ens, ii, jj), ref.pair_requests(m, ens, ii, jj), f"pairs measure {m}")
