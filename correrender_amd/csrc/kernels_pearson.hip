@@ -16,15 +16,12 @@
 // load instruction covers 64*VPT consecutive floats of ONE member volume (256 B / 512 B / 1 KiB contiguous), all
 // cs loads of a wave are issued back to back before the first use, so a wave has cs*256*VPT bytes in flight.
 // No LDS, no MFMA: ~4 flop/byte, HBM-read bound.
-#include <cstdlib>
-
 #include "crf_device.h"
 #include "crf_internal.h"
 
 namespace crf {
 
 constexpr int kPrepZeroFilled = 1280;  // a_e = 0 for cs <= e < this: the padded slots of the register and split kernels
-static_assert(kPrepZeroFilled >= kMaxRegisterMembers, "padded slots of the register kernels");
 
 // ---------------------------------------------------------------------------------------------------------
 // Reference-side preparation: one wave.  d_prep[e] = a_e for e < cs.
@@ -60,7 +57,7 @@ __global__ __launch_bounds__(256) void pearson_prep_kernel(RefSource src, const 
 // Per-voxel kernel, members resident in registers.
 //   CS_PAD  compile-time upper bound of cs (loops fully unrolled to it); EXACT: cs == CS_PAD, no guards; otherwise
 //           CS_PAD - pad_granule(CS_PAD) < cs < CS_PAD and only the last granule is guarded.
-//   VPT     voxels per lane (1, 2 or 4) = width of each global load in dwords.
+//   VPT     voxels per lane (1 or 2) = width of each global load in dwords.
 // ---------------------------------------------------------------------------------------------------------
 template <int VPT>
 struct VecT;
@@ -72,27 +69,19 @@ template <>
 struct VecT<2> {
     using type = float __attribute__((ext_vector_type(2)));
 };
-template <>
-struct VecT<4> {
-    using type = float __attribute__((ext_vector_type(4)));
-};
 
 // VPT consecutive voxels of one member for this lane (see crf_device.h: buffer descriptor + shared 32-bit offset).
-// NT selects the non-temporal policy: measured 0.753 -> 0.705 ms at 256^3 x 64 on MI355X (profiles/tuning_r01.md).
-template <int VPT, bool NT>
+// Non-temporal loads: measured 0.753 -> 0.705 ms at 256^3 x 64 on MI355X against the default policy
+// (profiles/tuning_r01.md).
+template <int VPT>
 __device__ __forceinline__ void load_vec(const float* base, uint32_t bytes, uint32_t byte_offset, float (&dst)[VPT]) {
     const auto rsrc = make_member_rsrc(base, bytes);
-    constexpr int aux = NT ? kAuxNonTemporal : 0;
     if constexpr (VPT == 1) {
-        dst[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, int(byte_offset), 0, aux));
-    } else if constexpr (VPT == 2) {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, int(byte_offset), 0, aux);
+        dst[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, int(byte_offset), 0, kAuxNonTemporal));
+    } else {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, int(byte_offset), 0, kAuxNonTemporal);
         dst[0] = __uint_as_float(v[0]);
         dst[1] = __uint_as_float(v[1]);
-    } else {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, int(byte_offset), 0, aux);
-#pragma unroll
-        for (int i = 0; i < 4; i++) dst[i] = __uint_as_float(v[i]);
     }
 }
 template <int VPT>
@@ -106,18 +95,17 @@ __device__ __forceinline__ void store_vec(float* p, const float (&src)[VPT]) {
 }
 
 // launch_pearson pads cs to the next multiple of this: only the last granule of a guarded instantiation can be padding
-constexpr int pad_granule(int cs_pad) {
-    return cs_pad <= 16 ? 8 : cs_pad <= 128 ? 16 : cs_pad <= 224 ? 32 : cs_pad <= 240 ? 16 : cs_pad <= 256 ? 8 : 64;
-}
+constexpr int pad_granule(int cs_pad) { return cs_pad <= 16 ? 8 : cs_pad <= 128 ? 16 : 32; }
 
-template <int CS_PAD, int VPT, bool EXACT, int MIN_WAVES, int BLOCK = 256, bool NT = true>
-__global__ __launch_bounds__(BLOCK, MIN_WAVES) void pearson_reg_kernel(const float* const* __restrict__ members,
-                                                                       const float* __restrict__ prep,
-                                                                       float* __restrict__ out, uint32_t num_voxels,
-                                                                       int cs) {
+template <int CS_PAD, int VPT, bool EXACT, int MIN_WAVES>
+__global__ __launch_bounds__(256, MIN_WAVES) void pearson_reg_kernel(const float* const* __restrict__ members,
+                                                                     const float* __restrict__ prep,
+                                                                     float* __restrict__ out, uint32_t num_voxels,
+                                                                     int cs) {
+    static_assert(CS_PAD <= kPrepZeroFilled, "a_e is zero-filled up to kPrepZeroFilled");
     constexpr int kFirstGuarded = EXACT ? CS_PAD : CS_PAD - pad_granule(CS_PAD);  // slots below are always members
     const auto is_member = [cs](int e) { return e < kFirstGuarded || e < cs; };      // folds in the unrolled loops
-    const uint32_t v0 = (blockIdx.x * BLOCK + threadIdx.x) * VPT;
+    const uint32_t v0 = (blockIdx.x * 256 + threadIdx.x) * VPT;
     const uint32_t byte_offset = v0 * 4u;       // one 32-bit offset serves all cs loads of the lane
     const uint32_t bytes = num_voxels * 4u;     // descriptor bound: lanes past the end read 0 and store nothing
     // Guarded instantiation (cs < CS_PAD), branch free: a padded slot loads at an out-of-range offset (the value is 0
@@ -129,15 +117,15 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void pearson_reg_kernel(const flo
 #pragma unroll
     for (int e = 0; e < CS_PAD; e++) {
         if (e < kFirstGuarded) {
-            load_vec<VPT, NT>(members[e], bytes, byte_offset, y[e]);
+            load_vec<VPT>(members[e], bytes, byte_offset, y[e]);
         } else if (CS_PAD >= 224) {
             // the widest kernels have no register to spare for per-slot offsets: a uniform branch around each of the
             // few guarded loads instead (they are the last loads issued)
 #pragma unroll
             for (int v = 0; v < VPT; v++) y[e][v] = 0.0f;
-            if (e < cs) load_vec<VPT, NT>(members[e], bytes, byte_offset, y[e]);
+            if (e < cs) load_vec<VPT>(members[e], bytes, byte_offset, y[e]);
         } else {
-            load_vec<VPT, NT>(members[e < cs ? e : cs - 1], bytes, e < cs ? byte_offset : kOutOfRangeOffset, y[e]);
+            load_vec<VPT>(members[e < cs ? e : cs - 1], bytes, e < cs ? byte_offset : kOutOfRangeOffset, y[e]);
         }
     }
     const float n = float(cs);
@@ -206,7 +194,7 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_reg_lds_kernel(const f
                                                                          const float* __restrict__ prep,
                                                                          float* __restrict__ out, uint32_t num_voxels,
                                                                          int cs) {
-    extern __shared__ float tail_dyn[];  // L rows of 256 floats (dynamic: 80 rows exceed the 64 KB static limit)
+    extern __shared__ float tail_dyn[];  // L rows of 256 floats
     float(*tail)[256] = reinterpret_cast<float(*)[256]>(tail_dyn);
     const uint32_t v0 = blockIdx.x * 256u + threadIdx.x;
     const uint32_t byte_offset = v0 * 4u, bytes = num_voxels * 4u;
@@ -276,9 +264,9 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_reg_lds_kernel(const f
 // ---------------------------------------------------------------------------------------------------------
 // 289..1216 members (r03): G = 2 or 4 LANES per voxel.  A wave owns 64 / G voxels; lane group g (lanes g * 64 / G ...)
 // holds members [g * S, g * S + S) of them, S = R + L slots per lane: R in registers and L in the lane's LDS column,
-// exactly the storage of the 176..320-member kernels above, which run at two waves per SIMD and 70-88 % of the HBM
+// exactly the storage of the 176..288-member kernels above, which run at two waves per SIMD and 70-88 % of the HBM
 // peak -- instead of one wave per SIMD with 384 values in VGPRs + AGPRs (37-56 %), an 8-wave relay through LDS
-// (385..512 members, 37 %) or three sweeps over the members (beyond 512: 3x the algorithmic bytes).
+// (385..512 members, 37 %; r02, since removed) or three sweeps over the members (beyond 512: 3x the algorithmic bytes).
 // The three passes of computePearson2<float> are sequential fp32 sums over the members, so each pass is a relay of
 // G stages inside the wave: in stage gg every lane runs the chain over its own S slots, starting from the value that
 // group gg - 1 handed over (ds_bpermute, no LDS memory), and only group gg's result is kept; the other groups compute
@@ -668,143 +656,6 @@ __device__ __forceinline__ void load_chunk_64(const float* const* __restrict__ m
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// 385..512 members, one HBM read (r02): a block of 8 waves holds ONE 64-voxel tile, wave w keeps members
-// [64 w, 64 w + 64) of it in registers.  The three passes of computePearson2<float> are sequential fp32 sums over the
-// members, so a pass runs as a relay: wave 0 adds its 64 terms, hands the running value to wave 1 through LDS, ... --
-// 8 stages per pass, a barrier between stages; what does not lie on the chain (deviations, quotients) is computed by
-// all waves at once between the passes.  Same operations in the same order as the reference, every member value
-// fetched once (pearson_big_kernel reads the volume three times: 3.0x the algorithmic bytes at the fabric counters).
-// Only one wave of a block works during a stage, and a lone wave issues a dependent fp32 chain slowly: the kernel is
-// bound by that latency, not by HBM -- 256x256x64: 385 / 512 members 2.72 / 2.91 ms (3.0 TB/s at 512) against 3.37 /
-// 4.39 ms for the three-pass kernel.  Two blocks per CU (128-register cap) overlap one block's loads with the other's
-// relay: 0.72 vs 1.68 ms at 128x128x64 x 400 with 143 registers and one block per CU.  With 128 members per wave
-// (513..1024 members) the relay loses to the three-pass kernel (2.40 vs 2.22 ms at 1000 members): not instantiated.
-// ---------------------------------------------------------------------------------------------------------
-template <int W, int R>
-__global__ __launch_bounds__(64 * W, 4)  // 4 waves per SIMD: 128 registers, two blocks per CU
-    void pearson_relay_kernel(const float* const* __restrict__ members,
-                                                               const float* __restrict__ prep,
-                                                               float* __restrict__ out, uint32_t num_voxels, int cs) {
-    // The products of a pass do not depend on the relay stage, so the compiler would hoist all R of them in front of the
-    // relay (R more registers; the 128-register cap then spills).  The scale factor is laundered through an empty asm
-    // inside the stage, which pins the products there.
-    constexpr bool kPinned = true;
-    __shared__ float s_relay[64];
-    const int lane = int(threadIdx.x & 63u);
-    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
-    const int e0 = wave * R;
-    const uint32_t bytes = num_voxels * 4u;
-    const float n = float(cs);
-    const float invN = 1.0f / n;
-    const float invNm1 = 1.0f / (n - 1.0f);
-    const uint32_t tiles = (num_voxels + 63u) / 64u;
-    // this wave's member pointers and a_e, one per lane and group of 64 members (handed out with v_readlane)
-    constexpr int G = R / 64;
-    uint32_t ptr_lo[G], ptr_hi[G];
-    float a_mine[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-        const int e = e0 + g * 64 + lane;
-        const uint64_t ptr = reinterpret_cast<uint64_t>(members[e < cs ? e : cs - 1]);
-        ptr_lo[g] = uint32_t(ptr);
-        ptr_hi[g] = uint32_t(ptr >> 32);
-        a_mine[g] = e < cs ? prep[e] : 0.0f;
-    }
-#pragma unroll 1
-    for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const uint32_t v0 = t * 64u + uint32_t(lane);
-        const uint32_t byte_offset = v0 * 4u;  // lanes past the end read 0 and store nothing
-        // (the member-count tests `e0 + i < cs` are uniform; left alone the compiler evaluates all R of them once, keeps
-        // them as SGPR pairs across the tile loop and spills those to VGPR lanes: the count is laundered per phase)
-        int cs_p = cs;
-        asm volatile("" : "+s"(cs_p));
-        float y[R];
-#pragma unroll
-        for (int i = 0; i < R; i++) {
-            const uint64_t base = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(ptr_hi[i / 64]), i % 64))) << 32) |
-                                  uint64_t(uint32_t(__builtin_amdgcn_readlane(int(ptr_lo[i / 64]), i % 64)));
-            y[i] = load_member_nt(reinterpret_cast<const float*>(base), bytes,
-                                  e0 + i < cs_p ? byte_offset : kOutOfRangeOffset);  // a slot past cs reads 0
-        }
-        // ---- pass 1: meanY += invN * y_e
-#pragma unroll 1
-        for (int s = 0; s < W; s++) {
-            if (wave == s) {
-                float m = s == 0 ? 0.0f : s_relay[lane];
-                float scale = invN;
-                if constexpr (kPinned) asm volatile("" : "+v"(scale));
-#pragma unroll
-                for (int i = 0; i < R; i++) m += scale * y[i];  // a padded slot adds invN * 0 = +0
-                s_relay[lane] = m;
-            }
-            __syncthreads();
-        }
-        const float meanY = s_relay[lane];
-        __syncthreads();
-        asm volatile("" : "+s"(cs_p));
-#pragma unroll
-        for (int i = 0; i < R; i++) {
-            y[i] = e0 + i < cs_p ? y[i] - meanY : 0.0f;
-            if (kPinned && (i & 7) == 7) __builtin_amdgcn_sched_barrier(0);  // in place, 8 at a time: register pressure
-        }
-        // ---- pass 2: varY += invNm1 * d * d
-#pragma unroll 1
-        for (int s = 0; s < W; s++) {
-            if (wave == s) {
-                float var = s == 0 ? 0.0f : s_relay[lane];
-                float scale = invNm1;
-                if constexpr (kPinned) asm volatile("" : "+v"(scale));
-#pragma unroll
-                for (int i = 0; i < R; i++) var += scale * y[i] * y[i];
-                s_relay[lane] = var;
-            }
-            __syncthreads();
-        }
-        const float sdY = sqrtf(s_relay[lane]);
-        __syncthreads();
-        if (__all(exact_div_guard(meanY, sdY))) {  // the same lanes in every wave of the block: one decision
-            const float rcp = 1.0f / sdY;
-#pragma unroll
-            for (int i = 0; i < R; i++) {
-                y[i] = exact_div(y[i], sdY, rcp);
-                if (kPinned && (i & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-            asm volatile("" : "+s"(cs_p));
-#pragma unroll
-            for (int i = 0; i < R; i++) {
-                y[i] = e0 + i < cs_p ? y[i] / sdY : 0.0f;
-                if (kPinned && (i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // ---- pass 3: r += a_e * ((y_e - meanY) / sdY)
-#pragma unroll 1
-        for (int s = 0; s < W; s++) {
-            if (wave == s) {
-                float r = s == 0 ? 0.0f : s_relay[lane];
-                asm volatile("" : "+s"(cs_p));
-                float a_lanes[G];
-#pragma unroll
-                for (int g = 0; g < G; g++) {
-                    a_lanes[g] = a_mine[g];
-                    if constexpr (kPinned) asm volatile("" : "+v"(a_lanes[g]));
-                }
-#pragma unroll
-                for (int i = 0; i < R; i++) {
-                    const float a =
-                        __uint_as_float(uint32_t(__builtin_amdgcn_readlane(int(__float_as_uint(a_lanes[i / 64])), i % 64)));
-                    if (e0 + i < cs_p) r += a * y[i];
-                }
-                s_relay[lane] = r;
-            }
-            __syncthreads();
-        }
-        if (wave == 0 && v0 < num_voxels) store_result_nt(out + v0, s_relay[lane]);
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(64) void pearson_big_kernel(const float* const* __restrict__ members,
                                                          const float* __restrict__ prep, float* __restrict__ out,
                                                          uint32_t num_voxels, int cs) {
@@ -858,60 +709,83 @@ __global__ void fill_kernel(float* __restrict__ out, size_t n, float value) {
 
 namespace {
 
-int env_int(const char* name, int fallback);
-
 template <int CS_PAD, int VPT>
 void launch_reg(const float* const* d_members, const float* d_prep, float* d_out, size_t blocks, size_t num_voxels,
                 int cs, hipStream_t s) {
     // occupancy request: data registers are CS_PAD*VPT per lane; ask for the waves/SIMD that budget allows.
+    // 161..224 values per lane: capped at 256 registers (two waves per SIMD) the kernel is 1.2x faster than with 256
+    // VGPRs + AGPRs at one wave per SIMD, which cannot overlap its load and compute phases -- measured at 512x512x128:
+    // 224 members 5.60 -> 4.63 ms (81 % of the HBM peak), 200 (guarded 224) 5.61 -> 4.53 ms.
     constexpr int kData = CS_PAD * VPT;
-    constexpr int kMinWaves = kData <= 64 ? 4 : (kData <= 128 ? 2 : 1);
-    // 161..256 values per lane: capped at 256 registers (two waves per SIMD; 12-120 B of scratch) the kernel is 1.2x
-    // faster than with 256 VGPRs + AGPRs at one wave per SIMD, which cannot overlap its load and compute phases --
-    // measured at 512x512x128: 256 members 8.15 -> 6.72 ms (64 % of the HBM peak), 224 members 5.60 -> 4.63 ms (81 %),
-    // 200 (guarded 224) 5.61 -> 4.53 ms.  The guarded 248 / 256 instantiations spill ~1 KB under the cap (28 ms): they stay
-    // at one wave.  CRF_PEARSON_WAVES=1 restores the one-wave kernels (tuning).
-    constexpr bool kTwoWavesExact = kData > 160 && kData <= 256;
-    constexpr bool kTwoWavesGuarded = kData > 160 && kData <= 240;
-    const bool two = env_int("CRF_PEARSON_WAVES", 2) == 2;
-    if (cs == CS_PAD) {
-        if constexpr (kTwoWavesExact) {
-            if (two) {
-                hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, true, 2>), dim3(unsigned(blocks)), dim3(256), 0, s,
-                                   d_members, d_prep, d_out, uint32_t(num_voxels), cs);
-                return;
-            }
-        }
+    constexpr int kMinWaves = kData <= 64 ? 4 : kData <= 128 ? 2 : kData <= 160 ? 1 : 2;
+    if (cs == CS_PAD)
         hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, true, kMinWaves>), dim3(unsigned(blocks)), dim3(256), 0, s,
                            d_members, d_prep, d_out, uint32_t(num_voxels), cs);
-    } else {
-        if constexpr (kTwoWavesGuarded) {
-            if (two) {
-                hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, false, 2>), dim3(unsigned(blocks)), dim3(256), 0, s,
-                                   d_members, d_prep, d_out, uint32_t(num_voxels), cs);
-                return;
-            }
-        }
+    else
         hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, false, kMinWaves>), dim3(unsigned(blocks)), dim3(256), 0,
                            s, d_members, d_prep, d_out, uint32_t(num_voxels), cs);
-    }
 }
 
 template <int CS_PAD>
 void launch_reg_vpt(int vpt, const float* const* d_members, const float* d_prep, float* d_out, size_t blocks,
                     size_t num_voxels, int cs, hipStream_t s) {
-    if constexpr (CS_PAD <= 64) {
-        if (vpt == 4) return launch_reg<CS_PAD, 4>(d_members, d_prep, d_out, blocks, num_voxels, cs, s);
-    }
-    if constexpr (CS_PAD <= 64 || CS_PAD == 128) {
-        if (vpt >= 2) return launch_reg<CS_PAD, 2>(d_members, d_prep, d_out, blocks, num_voxels, cs, s);
+    if constexpr (CS_PAD <= 16) {
+        if (vpt == 2) return launch_reg<CS_PAD, 2>(d_members, d_prep, d_out, blocks, num_voxels, cs, s);
     }
     return launch_reg<CS_PAD, 1>(d_members, d_prep, d_out, blocks, num_voxels, cs, s);
 }
 
-int env_int(const char* name, int fallback) {
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : fallback;
+// A per-voxel kernel with `rows` rows of 256 floats of dynamic LDS per block (pearson_reg_lds_kernel,
+// pearson_split_kernel).
+struct LdsKernel {
+    void (*kernel)(const float* const*, const float*, float*, uint32_t, int);
+    int rows;
+};
+
+// pearson_split_kernel at two waves per SIMD; the slots per lane are rounded up to a multiple of 16, so up to 16 * G of
+// them can be padding
+template <int R, int L, int G>
+LdsKernel split_kernel() {
+    return {pearson_split_kernel<R, L, G, 16 * G, 2>, L};
+}
+template <int R, int L>
+LdsKernel split_kernel(int lanes) {
+    return lanes == 2 ? split_kernel<R, L, 2>() : split_kernel<R, L, 4>();
+}
+
+// pearson_split_kernel for `slots` register + LDS slots per lane (160..304)
+LdsKernel split_kernel_for(int slots, int lanes) {
+    switch (slots) {
+        case 160: return split_kernel<160, 0>(lanes);  // 289..320 or 577..640 members
+        case 176: return split_kernel<176, 0>(lanes);
+        case 192: return split_kernel<192, 0>(lanes);
+        case 208: return split_kernel<208, 0>(lanes);
+        // beyond 208 slots the rest goes to LDS rows: with 224 register slots the allocation is at its edge and
+        // whether 16 B or 0.5 KB of scratch come out depends on details of the rare path (measured: 448 members
+        // 72 % of the peak without, 63 % with 52 B of scratch)
+        case 224: return split_kernel<208, 16>(lanes);
+        case 240: return split_kernel<216, 24>(lanes);
+        case 256: return split_kernel<216, 40>(lanes);
+        case 272: return split_kernel<216, 56>(lanes);
+        case 288: return split_kernel<216, 72>(lanes);
+        // 304 slots, four lanes only (1153..1216 members): 80 KB of LDS per block, still two blocks per CU
+        // (320 slots = 224 + 96 LDS rows: one block per CU, 17-32 % of the peak -- not instantiated)
+        default: return split_kernel<224, 80, 4>();
+    }
+}
+
+hipError_t launch_lds(LdsKernel k, size_t blocks, const float* const* d_members, const float* d_prep, float* d_out,
+                      size_t num_voxels, int cs, hipStream_t s) {
+    const size_t bytes = size_t(k.rows) * 256 * sizeof(float);
+    if (bytes > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
+        if (e != hipSuccess) return e;
+    }
+    if (blocks > 0)
+        hipLaunchKernelGGL(k.kernel, dim3(unsigned(blocks)), dim3(256), bytes, s, d_members, d_prep, d_out,
+                           uint32_t(num_voxels), cs);
+    return hipSuccess;
 }
 
 }  // namespace
@@ -937,21 +811,10 @@ namespace {
 template <int CS_PAD>
 void launch_symmetric(const float* const* mx, const float* const* my, int cs, size_t num_voxels, float* d_out,
                       hipStream_t s) {
-    constexpr int kMinWaves = CS_PAD <= 32 ? 4 : (CS_PAD <= 64 ? 2 : 1);
-    const unsigned blocks = unsigned((num_voxels + 255) / 256);
     // 2 * CS_PAD values per lane.  Two waves under a 256-register cap pay off at 96 (90 members: 2.55 -> 2.04 ms) but
     // not with the 72-670 B of scratch of the 112 / 128 instantiations (128 members: 3.92 -> 5.09 ms)
-    if constexpr (CS_PAD == 96) {
-        if (env_int("CRF_PEARSON_WAVES", 2) == 2) {
-            if (cs == CS_PAD)
-                hipLaunchKernelGGL((pearson_symmetric_kernel<CS_PAD, true, 2>), dim3(blocks), dim3(256), 0, s, mx, my,
-                                   d_out, uint32_t(num_voxels), cs, nullptr, uint32_t(num_voxels), 0, 0, 0);
-            else
-                hipLaunchKernelGGL((pearson_symmetric_kernel<CS_PAD, false, 2>), dim3(blocks), dim3(256), 0, s, mx, my,
-                                   d_out, uint32_t(num_voxels), cs, nullptr, uint32_t(num_voxels), 0, 0, 0);
-            return;
-        }
-    }
+    constexpr int kMinWaves = CS_PAD <= 32 ? 4 : (CS_PAD <= 64 || CS_PAD == 96 ? 2 : 1);
+    const unsigned blocks = unsigned((num_voxels + 255) / 256);
     if (cs == CS_PAD)
         hipLaunchKernelGGL((pearson_symmetric_kernel<CS_PAD, true, kMinWaves>), dim3(blocks), dim3(256), 0, s, mx, my,
                            d_out, uint32_t(num_voxels), cs, nullptr, uint32_t(num_voxels), 0, 0, 0);
@@ -1030,133 +893,18 @@ hipError_t launch_pearson(const float* const* d_members, int cs, size_t num_voxe
                            d_prep);
     if (!ref.run()) return hipGetLastError();
 
-    size_t covered = 0;
+    size_t covered = num_voxels;  // voxels the per-voxel kernel below answers; pearson_stream_kernel takes the rest
+    const char* name;
+    hipError_t e = hipSuccess;
     if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    // 289..1216 members: two (up to 576) or four lanes per voxel (pearson_split_kernel).  CRF_PEARSON_SPLIT=0 selects the
-    // r02 kernels (VGPRs + AGPRs at one wave per SIMD up to 384 members, the 8-wave relay up to 512, three sweeps beyond).
-    // From 289 members: measured at 512x512x128 against the one-lane kernels (registers + LDS rows), % of the HBM peak:
-    // 160 members 78 vs 83, 192: 76 vs 83, 224: 75 vs 83, 256: 73 vs 87, 288: 74 vs 79, 320: 74 vs 71
-    // (profiles/r03_pearson_two_lanes_from_129_members.txt).  CRF_PEARSON_SPLIT_FROM moves the threshold (>= 129; tuning).
-    const int split_from = env_int("CRF_PEARSON_SPLIT_FROM", 289);
-    if (cs >= split_from && cs > 128 && cs <= kSplitMaxMembers && env_int("CRF_PEARSON_SPLIT", 1) != 0) {
-        const int lanes = cs > 576 ? 4 : 2;  // (two lanes x 304 slots = 224 + 80 LDS rows: 0.5 KB of scratch per lane)
-        const int slots = ((cs + lanes - 1) / lanes + 15) / 16 * 16;  // per lane, in steps of 16: 160 .. 304
-        const size_t per_block = size_t(4) * (64 / lanes);
-        const size_t blocks_ = (num_voxels + per_block - 1) / per_block;
-        hipError_t attr = hipSuccess;
-        bool launched = false;
-#define CRF_LAUNCH_SPLIT(R_, L_, G_, W_)                                                                          \
-    {                                                                                                             \
-        constexpr size_t kBytes = size_t(L_) * 256 * sizeof(float);                                               \
-        const auto kern = &pearson_split_kernel<R_, L_, G_, 16 * G_, W_>;                                         \
-        if (kBytes > 64 * 1024)                                                                                   \
-            attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                       \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, int(kBytes));                  \
-        if (attr == hipSuccess && blocks_ > 0)                                                                    \
-            hipLaunchKernelGGL(kern, dim3(unsigned(blocks_)), dim3(256), kBytes, s, d_members, d_prep, d_out,      \
-                               uint32_t(num_voxels), cs);                                                         \
-        launched = attr == hipSuccess;                                                                            \
-    }
-#define CRF_LAUNCH_SPLIT_G(R_, L_, W_)                                                                            \
-    if (lanes == 2) CRF_LAUNCH_SPLIT(R_, L_, 2, W_) else CRF_LAUNCH_SPLIT(R_, L_, 4, W_)
-        switch (slots) {
-            case 80: CRF_LAUNCH_SPLIT(80, 0, 2, 4); break;    // (tuning: CRF_PEARSON_SPLIT_FROM)
-            case 96: CRF_LAUNCH_SPLIT(96, 0, 2, 4); break;
-            case 112: CRF_LAUNCH_SPLIT(112, 0, 2, 3); break;
-            case 128: CRF_LAUNCH_SPLIT(128, 0, 2, 3); break;
-            case 144: CRF_LAUNCH_SPLIT(144, 0, 2, 2); break;
-            case 160: if (lanes == 2) CRF_LAUNCH_SPLIT(160, 0, 2, 2) else CRF_LAUNCH_SPLIT(160, 0, 4, 2) break;  // 577..640 members
-            case 176: CRF_LAUNCH_SPLIT_G(176, 0, 2); break;
-            case 192: CRF_LAUNCH_SPLIT_G(192, 0, 2); break;
-            case 208: CRF_LAUNCH_SPLIT_G(208, 0, 2); break;
-            // beyond 208 slots the rest goes to LDS rows: with 224 register slots the allocation is at its edge and
-            // whether 16 B or 0.5 KB of scratch come out depends on details of the rare path (measured: 448 members
-            // 72 % of the peak without, 63 % with 52 B of scratch)
-            case 224: CRF_LAUNCH_SPLIT_G(208, 16, 2); break;
-            case 240: CRF_LAUNCH_SPLIT_G(216, 24, 2); break;
-            case 256: CRF_LAUNCH_SPLIT_G(216, 40, 2); break;
-            case 272: CRF_LAUNCH_SPLIT_G(216, 56, 2); break;
-            case 288: CRF_LAUNCH_SPLIT_G(216, 72, 2); break;
-            case 304: CRF_LAUNCH_SPLIT(224, 80, 4, 2); break;  // 80 KB of LDS per block: still two blocks per CU
-            // (320 slots = 224 + 96 LDS rows: one block per CU, 17-32 % of the peak -- not instantiated)
-            default: break;
-        }
-#undef CRF_LAUNCH_SPLIT_G
-#undef CRF_LAUNCH_SPLIT
-        if (launched) {
-            covered = num_voxels;
-            if (info) info->kernel_name = "pearson_split_kernel";
-            goto tail;
-        }
-    }
-    if (cs <= kMaxRegisterMembers) {
-        const int cs_pad = cs <= 8 ? 8 : cs <= 128 ? (cs + 15) / 16 * 16 : cs <= 224 ? (cs + 31) / 32 * 32
-                         : cs <= 240 ? 240 : cs <= 256 ? (cs + 7) / 8 * 8 : (cs + 63) / 64 * 64;
+    if (cs <= 224) {
+        const int cs_pad = cs <= 8 ? 8 : cs <= 128 ? (cs + 15) / 16 * 16 : (cs + 31) / 32 * 32;
         // voxels per lane.  Measured on MI355X at 256^3 x 64 (profiles/): one voxel per lane (dword loads, 93 VGPRs,
         // 5 waves/SIMD) reaches 5.7 TB/s; 2 per lane (196 VGPRs, 2 waves/SIMD) 4.9 TB/s; 4 per lane 3.4 TB/s --
-        // occupancy, not load width, is what keeps HBM busy here.  CRF_PEARSON_VPT overrides for tuning experiments.
-        int vpt = cs_pad <= 16 ? 2 : 1;
-        vpt = env_int("CRF_PEARSON_VPT", vpt);
-        if (vpt > max_vpt) vpt = max_vpt;
-        while (vpt > 1 && cs_pad * vpt > 256) vpt >>= 1;
-        if (cs_pad > 64 && cs_pad != 128) vpt = 1;  // wider loads are instantiated for the tuning sizes only
-        if (vpt != 1 && vpt != 2 && vpt != 4) vpt = 1;
-        const int variant = env_int("CRF_PEARSON_VARIANT", 0);
-        if (variant > 0 && cs == 64) {  // tuning experiments (tools/tune_pearson.py), one voxel per lane
-#define CRF_VARIANT(MINW, BLK, NT_)                                                                              \
-    {                                                                                                            \
-        const size_t blocks_ = (num_voxels + BLK - 1) / BLK;                                                     \
-        covered = num_voxels;                                                                                    \
-        if (blocks_ > 0)                                                                                         \
-            hipLaunchKernelGGL((pearson_reg_kernel<64, 1, true, MINW, BLK, NT_>), dim3(unsigned(blocks_)),       \
-                               dim3(BLK), 0, s, d_members, d_prep, d_out, uint32_t(num_voxels), cs);                        \
-    }
-            switch (variant) {
-                case 1: CRF_VARIANT(4, 256, false); break;  // temporal (default-policy) loads
-                case 2: CRF_VARIANT(2, 512, true); break;   // 512-thread blocks
-                case 3: CRF_VARIANT(6, 256, true); break;   // register cap for 6 waves/SIMD
-                case 4: CRF_VARIANT(4, 128, true); break;   // 128-thread blocks
-                case 5: CRF_VARIANT(4, 64, true); break;    // one wave per block
-                default: CRF_VARIANT(4, 256, true); break;
-            }
-#undef CRF_VARIANT
-            if (info) info->kernel_name = "pearson_reg_kernel";
-            goto tail;
-        }
-        // 241..320 members: 240 values in registers + the rest in the lane's LDS column (pearson_reg_lds_kernel); measured at
-        // 512x512x128: 256 members 85 % of the HBM peak (64 % with 256 register values under the two-wave cap, 53 % at one
-        // wave), 272: 82 % (57 %), 288: 78 % (54 %), 300: 71 % (54 %), 320: 69 % (59 %).  CRF_PEARSON_LDS_TAIL=0 selects the pure register kernels.
-        if (cs > 224 && cs <= 320 && env_int("CRF_PEARSON_LDS_TAIL", 1) != 0) {
-            const size_t blocks_ = (num_voxels + 255) / 256;
-            hipError_t attr = hipSuccess;
-#define CRF_LAUNCH_REG_LDS(R_, L_)                                                                                \
-    {                                                                                                             \
-        constexpr size_t kBytes = size_t(L_) * 256 * sizeof(float);                                               \
-        if (kBytes > 64 * 1024)                                                                                   \
-            attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&pearson_reg_lds_kernel<R_, L_, 2>),          \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, int(kBytes));                  \
-        if (attr == hipSuccess)                                                                                   \
-            hipLaunchKernelGGL((pearson_reg_lds_kernel<R_, L_, 2>), dim3(unsigned(blocks_)), dim3(256), kBytes, s,  \
-                               d_members, d_prep, d_out, uint32_t(num_voxels), cs);                               \
-    }
-            if (cs <= 240) {
-                CRF_LAUNCH_REG_LDS(224, 16)
-            } else if (cs <= 256) {
-                CRF_LAUNCH_REG_LDS(240, 16)
-            } else if (cs <= 288) {
-                CRF_LAUNCH_REG_LDS(240, 48)
-            } else {
-                CRF_LAUNCH_REG_LDS(240, 80)  // (144 rows for 321..384 were measured: one block per CU, 31-33 % -- not kept)
-            }
-#undef CRF_LAUNCH_REG_LDS
-            if (attr == hipSuccess) {
-                covered = num_voxels;
-                if (info) info->kernel_name = "pearson_reg_lds_kernel";
-                goto tail;
-            }
-        }
+        // occupancy, not load width, is what keeps HBM busy here.
+        const int vpt = cs_pad <= 16 && max_vpt >= 2 ? 2 : 1;
+        covered = num_voxels / vpt * vpt;  // whole vectors; the descriptor bounds the last block
         const size_t per_block = size_t(256) * vpt;
-        covered = num_voxels / vpt * vpt;                       // whole vectors; the descriptor bounds the last block
         const size_t blocks = (covered + per_block - 1) / per_block;
         if (blocks > 0) {
             switch (cs_pad) {
@@ -1171,44 +919,39 @@ hipError_t launch_pearson(const float* const* d_members, int cs, size_t num_voxe
                 case 128: launch_reg_vpt<128>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
                 case 160: launch_reg_vpt<160>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
                 case 192: launch_reg_vpt<192>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
-                case 224: launch_reg_vpt<224>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
-                case 240: launch_reg_vpt<240>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
-                case 248: launch_reg_vpt<248>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
-                case 256: launch_reg_vpt<256>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
-                case 320: launch_reg_vpt<320>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
-                default: launch_reg_vpt<384>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
+                default: launch_reg_vpt<224>(vpt, d_members, d_prep, d_out, blocks, num_voxels, cs, s); break;
             }
         }
-        if (info) info->kernel_name = "pearson_reg_kernel";
+        name = "pearson_reg_kernel";
+    } else if (cs <= 288) {
+        // 225..288 members: 224 or 240 values in registers + the rest in the lane's LDS column; measured at 512x512x128:
+        // 256 members 85 % of the HBM peak (64 % with 256 register values under the two-wave cap, 53 % at one wave),
+        // 272: 82 % (57 %), 288: 78 % (54 %).
+        const LdsKernel k = cs <= 240   ? LdsKernel{pearson_reg_lds_kernel<224, 16, 2>, 16}
+                            : cs <= 256 ? LdsKernel{pearson_reg_lds_kernel<240, 16, 2>, 16}
+                                        : LdsKernel{pearson_reg_lds_kernel<240, 48, 2>, 48};
+        e = launch_lds(k, (num_voxels + 255) / 256, d_members, d_prep, d_out, num_voxels, cs, s);
+        name = "pearson_reg_lds_kernel";
+    } else if (cs <= kSplitMaxMembers) {
+        // 289..1216 members: two (up to 576) or four lanes per voxel.  From 289 members: measured at 512x512x128
+        // against the one-lane kernels (registers + LDS rows), % of the HBM peak: 160 members 78 vs 83, 192: 76 vs 83,
+        // 224: 75 vs 83, 256: 73 vs 87, 288: 74 vs 79, 320: 74 vs 71 (profiles/r03_pearson_two_lanes_from_129_members.txt).
+        const int lanes = cs > 576 ? 4 : 2;  // (two lanes x 304 slots = 224 + 80 LDS rows: 0.5 KB of scratch per lane)
+        const int slots = ((cs + lanes - 1) / lanes + 15) / 16 * 16;  // per lane, in steps of 16: 160 .. 304
+        const size_t per_block = size_t(4) * (64 / lanes);
+        e = launch_lds(split_kernel_for(slots, lanes), (num_voxels + per_block - 1) / per_block, d_members, d_prep,
+                       d_out, num_voxels, cs, s);
+        name = "pearson_split_kernel";
     } else {
-        // chunked three-pass kernel (see pearson_big_kernel); CRF_PEARSON_BIG=0 selects the plain streaming kernel,
-        // CRF_PEARSON_BIG_WAVES overrides the grid (tuning)
-        if (cs <= 512 && env_int("CRF_PEARSON_RELAY", 1) != 0) {
-            // one block per 64-voxel tile at a time, as many blocks as the chip holds
-            const size_t tiles = (num_voxels + 63) / 64;
-            int per_cu = 1, device = 0, cus = 256;
-            (void)hipGetDevice(&device);
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pearson_relay_kernel<8, 64>, 512, 0);
-            const size_t want = size_t(cus) * size_t(per_cu > 0 ? per_cu : 1);
-            const unsigned blocks = unsigned(tiles < want ? tiles : want);
-            hipLaunchKernelGGL((pearson_relay_kernel<8, 64>), dim3(blocks), dim3(512), 0, s, d_members, d_prep, d_out,
-                               uint32_t(num_voxels), cs);
-            covered = num_voxels;
-            if (info) info->kernel_name = "pearson_relay_kernel";
-        } else if (env_int("CRF_PEARSON_BIG", 1) != 0) {
-            const size_t tiles = (num_voxels + 63) / 64;
-            const size_t want = size_t(env_int("CRF_PEARSON_BIG_WAVES", kBigWaves));
-            const unsigned blocks = unsigned(tiles < want ? tiles : want);
-            hipLaunchKernelGGL(pearson_big_kernel, dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out,
-                               uint32_t(num_voxels), cs);
-            covered = num_voxels;
-            if (info) info->kernel_name = "pearson_big_kernel";
-        } else if (info) {
-            info->kernel_name = "pearson_stream_kernel";
-        }
+        // chunked three-pass kernel (see pearson_big_kernel)
+        const size_t tiles = (num_voxels + 63) / 64;
+        const unsigned blocks = unsigned(tiles < size_t(kBigWaves) ? tiles : size_t(kBigWaves));
+        hipLaunchKernelGGL(pearson_big_kernel, dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out,
+                           uint32_t(num_voxels), cs);
+        name = "pearson_big_kernel";
     }
-tail:
+    if (e != hipSuccess) return e;
+    if (info) info->kernel_name = name;
     if (covered < num_voxels) {
         const size_t rest = num_voxels - covered;
         hipLaunchKernelGGL(pearson_stream_kernel, dim3(unsigned((rest + 255) / 256)), dim3(256), 0, s, d_members,

@@ -21,14 +21,24 @@ def _run(engine, oracle, ens, ref_xyz):
     return got.reshape(-1), want
 
 
+def _kernel(cs):
+    """The per-voxel kernel launch_pearson runs for cs >= 2 members."""
+    if cs <= 224:
+        return "pearson_reg_kernel"
+    if cs <= 288:
+        return "pearson_reg_lds_kernel"
+    return "pearson_split_kernel" if cs <= 1216 else "pearson_big_kernel"
+
+
 @pytest.mark.parametrize("cs", [2, 3, 8, 9, 16, 17, 31, 32, 33, 48, 56, 64, 65, 72, 80, 96, 100, 112, 128, 130, 150, 160,
-                                192, 200, 224, 250, 256, 257, 300, 320, 383, 384, 385, 450, 511, 512, 513, 577, 700, 1000,
-                                1023, 1024, 1025, 1100])
+                                192, 200, 224, 225, 240, 241, 250, 256, 257, 288, 300, 320, 383, 384, 385, 450, 511, 512, 513,
+                                577, 700, 1000, 1023, 1024, 1025, 1100])
 def test_pearson_member_counts(engine, oracle, cs):
     # 20*12*9 = 2160 voxels: not a multiple of any block size -> exercises the ragged tail as well
     ens = synth.box_ensemble(20, 12, 9, cs, seed=cs)
     got, want = _run(engine, oracle, ens, (5, 6, 4))
     assert_bit_exact(got, want, f"pearson cs={cs}")
+    assert engine.last_kernel_name() == _kernel(cs)
 
 
 def test_pearson_config0_64cubed_16_members(engine, oracle):
@@ -108,7 +118,7 @@ def test_pearson_lanes_per_voxel_kernel_boundaries(engine, oracle, cs):
     ens = synth.box_ensemble(20, 12, 9, cs, seed=cs)
     got, want = _run(engine, oracle, ens, (7, 3, 2))
     assert_bit_exact(got, want, f"pearson cs={cs}")
-    assert engine.last_kernel_name() == ("pearson_split_kernel" if 288 < cs <= 1216 else "pearson_big_kernel")
+    assert engine.last_kernel_name() == _kernel(cs)
 
 
 @pytest.mark.parametrize("cs", [340, 500, 650, 1000])
@@ -153,6 +163,7 @@ def test_pearson_means_that_are_exactly_zero(engine, oracle, cs):
     ens = ens.reshape(cs, zs, ys, xs)
     got, want = _run(engine, oracle, ens, (3, 2, 3))    # a reference voxel of ordinary magnitude
     assert_bit_exact(got, want, f"pearson zero means cs={cs}")
+    assert engine.last_kernel_name() == _kernel(cs)
     assert np.isfinite(want[: n // 4]).all() and not np.isfinite(want[n // 4:n // 2]).any()
 
 
@@ -174,3 +185,4 @@ def test_pearson_magnitude_sweep_bit_exact(engine, oracle, cs):
         ens = (base * scale + offset).astype(np.float32).reshape(cs, zs, ys, xs)
     got, want = _run(engine, oracle, ens, (3, 2, 1))
     assert_bit_exact(got, want, f"pearson magnitude sweep cs={cs}")
+    assert engine.last_kernel_name() == _kernel(cs)
