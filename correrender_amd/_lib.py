@@ -82,6 +82,9 @@ SYMBOLS = {
     "crf_set_profiling": (C.c_int, [_VOIDP, C.c_int]),
     "crf_take_kernel_time": (C.c_int, [_VOIDP, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "crf_last_kernel_name": (C.c_char_p, [_VOIDP]),
+    "crf_set_member_layout": (C.c_int, [_VOIDP, C.c_int]),
+    "crf_last_member_layout": (C.c_int, [_VOIDP]),
+    "crf_members_changed": (C.c_int, [_VOIDP]),
     "crf_synth_box_member": (C.c_int, [_VOIDP, _VOIDP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_uint64, _VOIDP]),
     "crf_set_kraskov_noise": (C.c_int, [_VOIDP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -63,11 +63,20 @@ int bind_device(crf_context* c) {
     return CRF_OK;
 }
 
+// the packed copy of the members (crf_internal.h); decided again at the next Pearson field evaluation
+void drop_packed(crf_context* c) {
+    if (c->d_packed) (void)hipFree(c->d_packed);
+    c->d_packed = nullptr;
+    c->packed_bytes = 0;
+    c->pack_state = 0;
+}
+
 void release_members(crf_context* c) {
     if (c->owned_block) (void)hipFree(c->owned_block);
     c->owned_block = nullptr;
     c->members.clear();
     c->minmax_valid = false;
+    drop_packed(c);
 }
 
 void release_secondary(crf_context* c) {
@@ -92,6 +101,56 @@ int install_member_table(crf_context* c) {
     c->minmax_valid = false;
     c->host_chunks = 0;  // the per-range pointer tables of the host-output path describe the old members
     c->windows = 0;      // ... and so do the window tables of a >= 4 GiB grid
+    drop_packed(c);      // ... and the packed copy their values
+    return CRF_OK;
+}
+
+// Packs the members for the Pearson field if the layout policy asks for it (include/corrfield.h: crf_member_layout),
+// once per set of members, on stream s.  *use: the packed copy is there for this evaluation.
+int ensure_packed(crf_context* c, hipStream_t s, crf::PackedMembers* use) {
+    *use = crf::PackedMembers{};
+    const int cs = c->cs;
+    if (c->member_layout == CRF_MEMBER_LAYOUT_RAW || cs < crf::kPackMinMembers || cs > crf::kPackMaxMembers ||
+        c->windowed || c->num_voxels != c->alloc_voxels)
+        return CRF_OK;
+    const bool automatic = c->member_layout == CRF_MEMBER_LAYOUT_AUTO;
+    const size_t tiles = (c->num_voxels + 63) / 64;
+    const size_t header_bytes = (tiles * size_t(crf::pack_slots(cs)) + 255) & ~size_t(255);
+    if (c->pack_state == 0) {
+        c->pack_state = -1;
+        if (automatic && c->num_voxels < (size_t(1) << 20)) return CRF_OK;  // the one-time encode would not pay off
+        // padded slots are stored and read: near the bottom of a 16-slot granule the copy moves more than the members
+        if (automatic && crf::pack_voxel_bytes(cs) > crf::kPackAutoByteRatio * double(4 * cs + 4)) return CRF_OK;
+        const size_t bytes = header_bytes + tiles * size_t(crf::pack_tile_bytes(crf::pack_slots(cs)));
+        if (automatic) {
+            size_t free_b = 0, total_b = 0;
+            CRF_HIP(c, hipMemGetInfo(&free_b, &total_b));
+            const size_t keep = std::max(size_t(8) << 30, total_b / 10);
+            if (free_b < bytes || free_b - bytes < keep) return CRF_OK;
+        }
+        if (!c->d_pack_fallbacks)
+            CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_pack_fallbacks), sizeof(uint32_t)));
+        if (hipMalloc(reinterpret_cast<void**>(&c->d_packed), bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            c->d_packed = nullptr;
+            if (automatic) return CRF_OK;
+            return fail(c, CRF_ERR_DEVICE, fmt("no device memory for the packed members (%zu bytes)", bytes));
+        }
+        c->packed_bytes = bytes;
+        CRF_HIP(c, hipMemsetAsync(c->d_pack_fallbacks, 0, sizeof(uint32_t), s));
+        CRF_HIP(c, crf::launch_pack_members(c->d_member_table, cs, c->num_voxels, c->d_packed, c->d_packed + header_bytes,
+                                            c->d_pack_fallbacks, s));
+        uint32_t fallbacks = 0;
+        CRF_HIP(c, hipMemcpyAsync(&fallbacks, c->d_pack_fallbacks, sizeof fallbacks, hipMemcpyDeviceToHost, s));
+        CRF_HIP(c, hipStreamSynchronize(s));
+        if (automatic && double(fallbacks) > 0.05 * double(tiles) * double(cs)) {
+            drop_packed(c);
+            c->pack_state = -1;
+            return CRF_OK;
+        }
+        c->pack_state = 1;
+    }
+    if (c->pack_state == 1) *use = crf::PackedMembers{c->d_packed, c->d_packed + header_bytes};
     return CRF_OK;
 }
 
@@ -230,6 +289,7 @@ void crf_destroy(crf_context* c) {
     if (c->d_requests) (void)hipFree(c->d_requests);
     if (c->d_request_out) (void)hipFree(c->d_request_out);
     if (c->d_minmax) (void)hipFree(c->d_minmax);
+    if (c->d_pack_fallbacks) (void)hipFree(c->d_pack_fallbacks);
     if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
     c->copy_pool.reset();
     if (c->h_staging) (void)hipHostFree(c->h_staging);
@@ -842,10 +902,15 @@ static int compute_impl_one(crf_context* c, const crf_params* p, const void* dev
         return CRF_OK;
     }
     switch (p->measure) {
-        case CRF_PEARSON:
+        case CRF_PEARSON: {
+            crf::PackedMembers packed;
+            if (phase & 2u)
+                if (int r = ensure_packed(c, s, &packed)) return r;
             e = crf::launch_pearson(c->d_member_table, c->cs, c->num_voxels, vpt, ref, prep, out, s, e0, e1,
-                                    &info);
+                                    &info, packed);
+            if (phase & 2u) c->last_layout = packed.header ? CRF_MEMBER_LAYOUT_PACKED : CRF_MEMBER_LAYOUT_RAW;
             break;
+        }
         case CRF_SPEARMAN:
             if (c->cs > crf::kMaxSortMembers)
                 return fail(c, CRF_ERR_UNSUPPORTED, fmt("Spearman supports at most %d members", crf::kMaxSortMembers));
@@ -1465,6 +1530,32 @@ int crf_take_kernel_time(crf_context* c, double* out_ms_sum, int* out_launches) 
 }
 
 const char* crf_last_kernel_name(const crf_context* c) { return c ? c->last_kernel.c_str() : ""; }
+
+int crf_set_member_layout(crf_context* c, int mode) {
+    if (!c) return CRF_ERR_ARGUMENT;
+    if (mode != CRF_MEMBER_LAYOUT_AUTO && mode != CRF_MEMBER_LAYOUT_RAW && mode != CRF_MEMBER_LAYOUT_PACKED)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("unknown member layout %d", mode));
+    if (mode == c->member_layout) return CRF_OK;
+    if (int r = bind_device(c)) return r;
+    CRF_HIP(c, hipDeviceSynchronize());  // evaluations in flight may still read the packed copy
+    drop_packed(c);
+    c->member_layout = mode;
+    return CRF_OK;
+}
+
+int crf_last_member_layout(const crf_context* c) { return c ? c->last_layout : CRF_MEMBER_LAYOUT_RAW; }
+
+int crf_members_changed(crf_context* c) {
+    if (!c) return CRF_ERR_ARGUMENT;
+    if (int r = bind_device(c)) return r;
+    CRF_HIP(c, hipDeviceSynchronize());  // evaluations in flight may still read what is dropped
+    c->minmax_valid = false;
+    c->sec_minmax_valid = false;
+    c->host_chunks = 0;
+    c->windows = 0;
+    drop_packed(c);
+    return CRF_OK;
+}
 
 int crf_synth_box_member(crf_context* c, void* device_out, int xs, int ys, int zs_local, int z_begin, int zs_global,
                          int member, int cs, uint64_t seed, void* stream) {

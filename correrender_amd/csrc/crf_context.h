@@ -47,6 +47,14 @@ struct crf_context {
     size_t request_capacity = 0;
     uint32_t* d_minmax = nullptr;
     bool minmax_valid = false;
+    // packed copy of the members for the Pearson field (crf_internal.h), built lazily at the first Pearson field
+    // evaluation after the members change (api.cpp: ensure_packed)
+    int member_layout = CRF_MEMBER_LAYOUT_AUTO;  // crf_set_member_layout
+    int pack_state = 0;                          // 0: not decided for the current members, 1: packed, -1: declined
+    unsigned char* d_packed = nullptr;           // header, then body (one allocation)
+    size_t packed_bytes = 0;
+    uint32_t* d_pack_fallbacks = nullptr;
+    int last_layout = CRF_MEMBER_LAYOUT_RAW;     // of the last Pearson field evaluation
     float min_v = 0.f, max_v = 0.f;
     // profiling
     bool profiling = false;

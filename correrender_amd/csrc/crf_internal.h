@@ -56,12 +56,100 @@ float minmax_key_to_float(uint32_t key);
 hipError_t launch_synth_box_member(float* d_out, int xs, int ys, int zs_local, int z_begin, int zs_global, int c,
                                    int cs, uint64_t seed, hipStream_t s);
 
+// ---- packed members (kernels_pearson.hip: pearson_encode_kernel, pearson_reg_kernel<..., true>) -------------------
+// A lossless 28-bit copy of the members for the Pearson field at kPackMinMembers..kPackMaxMembers members.  The grid is
+// cut into tiles of 64 consecutive voxels (one wave of the field kernel); a SEGMENT is one member of one tile.  An fp32
+// value (sign s, exponent field E, mantissa m) is stored as
+//     lo16   m & 0xFFFF                                  (16 bits)
+//     byte   s << 7 | m >> 16                            (8 bits)
+//     code   0 if E == 0 (+-0, denormals), else E - base + 1 in 1..15   (4 bits)
+// with one base byte per segment: the smallest non-zero E of the segment.  A segment fits if it holds no E == 255
+// (NaN, +-Inf) and its non-zero exponents span at most 15 binades; one that does not gets the header byte
+// kPackFallback and the field kernel reads it from the original member instead (its planes hold zeros).
+//
+// Memory: P = pack_slots(cs) slots per tile (cs rounded up to 16; slots cs..P-1 are padding: base 1, value +0).
+//   header   tiles x P bytes, tile t at t * P: the P base bytes (read by the field kernel with scalar loads)
+//   body     tiles x pack_tile_bytes(P), tile t at t * pack_tile_bytes(P), 1 KiB RUNS of 64 lanes x 16 B (lane l of the
+//            wave = voxel 64 t + l owns bytes [16 l, 16 l + 16) of every run; one dwordx4 load per run and wave):
+//     lo16 runs   P / 8       run r: member 8 r + i at bytes 2 i, 2 i + 1 of the lane's 16 B (little endian)
+//     byte runs   P / 16      run r: member 16 r + i at byte i
+//     code runs   (P + 31)/32 run r: member 32 r + i at bits 4 (i % 8) .. 4 (i % 8) + 3 of dword i / 8
+//   in that order.  Lanes past the end of the grid hold zeros.  Every slot is stored and read, padding included:
+//   pack_voxel_bytes(cs) = pack_tile_bytes(P) / 64 + P / 64 + 4 (result) per voxel against 4 cs + 4 from the members
+//   themselves -- 229 against 260 B at 64 members, but 116.5 against 72 B at 17 (see kPackAutoByteRatio).
+constexpr int kPackMinMembers = 17;
+constexpr int kPackMaxMembers = 128;
+constexpr uint32_t kPackFallback = 0xFFu;
+__host__ __device__ inline int pack_slots(int cs) { return (cs + 15) / 16 * 16; }
+__host__ __device__ inline int pack_lo_runs(int slots) { return slots / 8; }
+__host__ __device__ inline int pack_byte_runs(int slots) { return slots / 16; }
+__host__ __device__ inline int pack_code_runs(int slots) { return (slots + 31) / 32; }
+__host__ __device__ inline uint32_t pack_tile_bytes(int slots) {
+    return 1024u * uint32_t(pack_lo_runs(slots) + pack_byte_runs(slots) + pack_code_runs(slots));
+}
+// HBM bytes per voxel of one evaluation from the packed copy (members + base bytes + result)
+inline double pack_voxel_bytes(int cs) {
+    const int slots = pack_slots(cs);
+    return double(pack_tile_bytes(slots) + uint32_t(slots)) / 64.0 + 4.0;
+}
+// AUTO packs only where pack_voxel_bytes(cs) <= this x (4 cs + 4).  Measured on MI355X at 256^3, kernel time packed / raw
+// against the byte ratio (profiles/packed_members_layout_sweep.md): byte ratios of 0.88-0.92 gave 0.85-0.93 (7-15 %
+// faster) at every count tried, 0.94 gave 0.93-1.00, about 1.0 gave 0.98-1.05, and above that up to 1.56.
+constexpr double kPackAutoByteRatio = 0.925;
+// base byte of a segment from the smallest and largest non-zero exponent field of its values (emin = 256 when every
+// value is +-0 or denormal) and whether any value is NaN or +-Inf
+__host__ __device__ inline uint32_t pack_segment_base(uint32_t emin, uint32_t emax, bool special) {
+    if (special) return kPackFallback;
+    if (emin > 254u) return 1u;
+    return emax - emin <= 14u ? emin : kPackFallback;
+}
+__host__ __device__ inline uint32_t pack_lo16(uint32_t bits) { return bits & 0xFFFFu; }
+__host__ __device__ inline uint32_t pack_byte(uint32_t bits) { return ((bits >> 24) & 0x80u) | ((bits >> 16) & 0x7Fu); }
+__host__ __device__ inline uint32_t pack_code(uint32_t bits, uint32_t base) {
+    const uint32_t e = (bits >> 23) & 0xFFu;
+    return e == 0u ? 0u : e - base + 1u;
+}
+// v_perm_b32: byte i of the result is byte sel_i (0..7) of the 64-bit {hi, lo}
+__host__ __device__ inline uint32_t perm_bytes(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t d = (uint64_t(hi) << 32) | lo;
+    uint32_t r = 0;
+    for (int i = 0; i < 4; i++) r |= uint32_t((d >> (8 * ((sel >> (8 * i)) & 7u))) & 0xFFu) << (8 * i);
+    return r;
+#endif
+}
+// The value of a fitting segment from its three parts, each taken out of the word the field kernel loads: lo16 is half
+// `h` of lo_word, the byte is byte `b` of byte_word, the code is nibble `n` of code_word.  In the field kernel the
+// positions are compile-time constants: v_perm_b32 puts lo16 at the bottom and the byte twice above it (its top bit
+// lands on the sign, its low 7 bits on the top of the mantissa), v_bfe_u32 takes the code, an add-shift and a select
+// make the exponent field, v_bfi_b32 merges it -- 6 VALU per value.
+__host__ __device__ inline uint32_t unpack_bits(uint32_t lo_word, int h, uint32_t byte_word, int b, uint32_t code_word,
+                                                int n, uint32_t base) {
+    const uint32_t sel = uint32_t(2 * h) | uint32_t(2 * h + 1) << 8 | uint32_t(4 + b) << 16 | uint32_t(4 + b) << 24;
+    const uint32_t w = perm_bytes(byte_word, lo_word, sel);
+    const uint32_t code = (code_word >> (4 * n)) & 0xFu;
+    const uint32_t e = code != 0u ? (code + base - 1u) << 23 : 0u;
+    return (w & 0x807FFFFFu) | e;
+}
+
 // ---- kernels_pearson.hip ----------------------------------------------------------------------------------
+// The packed copy of a context's members (see above), or both null: the field kernel reads the members themselves.
+struct PackedMembers {
+    const unsigned char* header = nullptr;
+    const unsigned char* body = nullptr;
+};
 // d_ref: cs reference values on the device.  d_prep: scratch of kPrepBytes.  Writes num_voxels floats to d_out.
 // max_vpt: widest per-lane vector (1, 2 or 4 floats) the member/output pointers are aligned for.
+// packed: a packed copy of d_members (header non-null) for kPackMinMembers <= cs <= kPackMaxMembers, else ignored.
 hipError_t launch_pearson(const float* const* d_members, int cs, size_t num_voxels, int max_vpt, const RefSource& ref,
                           float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
-                          LaunchInfo* info);
+                          LaunchInfo* info, const PackedMembers& packed = PackedMembers{});
+// Builds the packed copy of d_members into header (tiles x pack_slots(cs) bytes) and body (tiles x pack_tile_bytes),
+// tiles = ceil(num_voxels / 64), and adds the number of member segments that fall back to *d_fallbacks.
+hipError_t launch_pack_members(const float* const* d_members, int cs, size_t num_voxels, unsigned char* header,
+                               unsigned char* body, uint32_t* d_fallbacks, hipStream_t s);
 hipError_t launch_fill(float* d_out, size_t n, float value, hipStream_t s);
 hipError_t launch_abs(float* d_out, size_t n, hipStream_t s);  // in place |.| (CRF_FLAG_ABSOLUTE_VALUE on a field)
 

@@ -97,12 +97,26 @@ __device__ __forceinline__ void store_vec(float* p, const float (&src)[VPT]) {
 // launch_pearson pads cs to the next multiple of this: only the last granule of a guarded instantiation can be padding
 constexpr int pad_granule(int cs_pad) { return cs_pad <= 16 ? 8 : cs_pad <= 128 ? 16 : 32; }
 
-template <int CS_PAD, int VPT, bool EXACT, int MIN_WAVES>
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+
+template <int CS_PAD, bool EXACT>
+__device__ __forceinline__ void pearson_packed_wave(const float* const* __restrict__ members,
+                                                    const float* __restrict__ prep, float* __restrict__ out,
+                                                    uint32_t num_voxels, int cs, const PackedMembers& packed);
+
+// PACKED: the members come from their packed copy (crf_internal.h; pearson_packed_wave below), VPT = 1.
+template <int CS_PAD, int VPT, bool EXACT, int MIN_WAVES, bool PACKED>
 __global__ __launch_bounds__(256, MIN_WAVES) void pearson_reg_kernel(const float* const* __restrict__ members,
                                                                      const float* __restrict__ prep,
                                                                      float* __restrict__ out, uint32_t num_voxels,
-                                                                     int cs) {
+                                                                     int cs, PackedMembers packed) {
     static_assert(CS_PAD <= kPrepZeroFilled, "a_e is zero-filled up to kPrepZeroFilled");
+    if constexpr (PACKED) {
+        static_assert(VPT == 1, "one voxel per lane: a wave is one 64-voxel tile of the packed copy");
+        pearson_packed_wave<CS_PAD, EXACT>(members, prep, out, num_voxels, cs, packed);
+        return;
+    }
     constexpr int kFirstGuarded = EXACT ? CS_PAD : CS_PAD - pad_granule(CS_PAD);  // slots below are always members
     const auto is_member = [cs](int e) { return e < kFirstGuarded || e < cs; };      // folds in the unrolled loops
     const uint32_t v0 = (blockIdx.x * 256 + threadIdx.x) * VPT;
@@ -181,6 +195,185 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_reg_kernel(const float
         }
     }
     if (v0 + VPT <= num_voxels) store_vec<VPT>(out + v0, r);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// pearson_reg_kernel on the packed copy (crf_internal.h): one wave = one 64-voxel tile.  The wave reads the tile's
+// CS_PAD base bytes with scalar loads and its 1 KiB runs with one dwordx4 buffer load each (all issued before the first
+// use, as the cs member loads of the raw form), then decodes every value.  A tile with a segment that did not fit then
+// reads that member from the member itself, in a uniform branch (the decode itself has no branches).  The arithmetic is the raw form's, operation for operation, with what
+// is off the sequential sums done two slots at a time in packed fp32 (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32: the
+// same IEEE operations per element, as in pearson_split_kernel) to make room for the decode.
+// ---------------------------------------------------------------------------------------------------------
+template <int CS_PAD, bool EXACT>
+__device__ __forceinline__ void pearson_packed_wave(const float* const* __restrict__ members,
+                                                    const float* __restrict__ prep, float* __restrict__ out,
+                                                    uint32_t num_voxels, int cs, const PackedMembers& packed) {
+    static_assert(CS_PAD % 16 == 0 && CS_PAD >= 32 && CS_PAD <= kPackMaxMembers, "pack_slots() of a packed cs");
+    constexpr int kLo = CS_PAD / 8, kByte = CS_PAD / 16, kCode = (CS_PAD + 31) / 32;
+    constexpr uint32_t kTileBytes = 1024u * uint32_t(kLo + kByte + kCode);
+    constexpr int kFirstGuarded = EXACT ? CS_PAD : CS_PAD - 16;
+    const auto is_member = [cs](int e) { return e < kFirstGuarded || e < cs; };
+    const uint32_t tile = blockIdx.x * 4u + uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+    if (tile >= (num_voxels + 63u) / 64u) return;  // the last block's surplus waves
+    const uint32_t v0 = tile * 64u + (threadIdx.x & 63u);
+    const uint32_t byte_offset = v0 * 4u, bytes = num_voxels * 4u;  // fallback members: lanes past the end read 0
+    const uint32_t* header = reinterpret_cast<const uint32_t*>(packed.header + size_t(tile) * CS_PAD);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(packed.body) + size_t(tile) * kTileBytes,
+                                                        short(0), int(kTileBytes), 0x00020000);
+    const int lane_bytes = int(threadIdx.x & 63u) * 16;
+    u4 code[kCode], byte[kByte], lo[kLo];
+    // issue order = order of first use (the first members need code run 0, byte run 0, lo run 0)
+#pragma unroll
+    for (int r = 0; r < kCode; r++)
+        code[r] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_bytes + 1024 * (kLo + kByte + r), 0, kAuxNonTemporal);
+#pragma unroll
+    for (int r = 0; r < kLo; r++) {
+        if (r % 2 == 0)
+            byte[r / 2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_bytes + 1024 * (kLo + r / 2), 0, kAuxNonTemporal);
+        lo[r] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_bytes + 1024 * r, 0, kAuxNonTemporal);
+    }
+    uint32_t hdr[CS_PAD / 4];  // base bytes, wave-uniform (SGPRs)
+    uint32_t fallback = 0;     // non-zero: some segment of the tile is read from its member
+#pragma unroll
+    for (int i = 0; i < CS_PAD / 4; i++) {
+        hdr[i] = header[i];
+        const uint32_t t = ~hdr[i];  // a byte of kPackFallback is a zero byte of t
+        fallback |= (t - 0x01010101u) & ~t & 0x80808080u;
+    }
+    f2 y[CS_PAD / 2];
+#pragma unroll
+    for (int e = 0; e < CS_PAD; e++)  // (a fallback segment decodes to 0 here: its planes hold zeros)
+        y[e / 2][e % 2] = __uint_as_float(unpack_bits(lo[e / 8][(e % 8) / 2], e % 2, byte[e / 16][(e % 16) / 4], e % 4,
+                                                      code[e / 32][(e % 32) / 8], e % 8, (hdr[e / 4] >> (8 * (e % 4))) & 0xFFu));
+    if (fallback != 0u) {  // uniform; about a third of the tiles of the benchmark's ensemble, one or two members each
+#pragma unroll
+        for (int e = 0; e < CS_PAD; e++) {
+            if (((hdr[e / 4] >> (8 * (e % 4))) & 0xFFu) == kPackFallback)  // never a padded slot (base 1)
+                y[e / 2][e % 2] = load_member_nt(members[e < kFirstGuarded || e < cs ? e : cs - 1], bytes, byte_offset);
+        }
+    }
+    const float n = float(cs);
+    const float invN = 1.0f / n;
+    const float invNm1 = 1.0f / (n - 1.0f);
+    // pass 1: meanY += invN * y_e (a padded slot is +0 and adds +0)
+    float meanY = 0.0f;
+    {
+        const f2 scale = {invN, invN};
+#pragma unroll
+        for (int k = 0; k < CS_PAD / 2; k++) {
+            const f2 t = scale * y[k];
+            meanY += t[0];
+            meanY += t[1];
+        }
+    }
+    // deviations in place (needed again, bit-identically, by pass 3); a padded slot's is forced to 0
+    {
+        const f2 mean2 = {meanY, meanY};
+#pragma unroll
+        for (int k = 0; k < CS_PAD / 2; k++) {
+            f2 d = y[k] - mean2;
+            if (2 * k >= kFirstGuarded) {
+                if (!is_member(2 * k)) d[0] = 0.0f;
+                if (!is_member(2 * k + 1)) d[1] = 0.0f;
+            }
+            y[k] = d;
+        }
+    }
+    // pass 2: varY += (invNm1 * d_e) * d_e
+    float varY = 0.0f;
+    {
+        const f2 scale = {invNm1, invNm1};
+#pragma unroll
+        for (int k = 0; k < CS_PAD / 2; k++) {
+            const f2 t = (scale * y[k]) * y[k];
+            varY += t[0];
+            varY += t[1];
+        }
+    }
+    const float sdY = sqrtf(varY);
+    float r = 0.0f;
+    if (__all(exact_div_guard(meanY, sdY))) {  // exact_div (crf_device.h) two slots at a time, then r += a_e * q_e
+        const float rcp = 1.0f / sdY;
+        const f2 rcp2 = {rcp, rcp}, sd2 = {sdY, sdY};
+#pragma unroll
+        for (int k = 0; k < CS_PAD / 2; k++) {
+            const f2 q0 = y[k] * rcp2;
+            const f2 rem = __builtin_elementwise_fma(-q0, sd2, y[k]);
+            const f2 q = __builtin_elementwise_fma(rem, rcp2, q0);
+            const f2 a = {prep[2 * k], prep[2 * k + 1]};
+            const f2 t = a * q;
+            r += t[0];
+            r += t[1];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < CS_PAD; e++) r += prep[e] * (is_member(e) ? y[e / 2][e % 2] / sdY : 0.0f);
+    }
+    if (v0 < num_voxels) store_result_nt(out + v0, r);
+}
+
+// The packed copy (crf_internal.h), built once per set of members: one wave per tile, one member at a time (the
+// segment's exponent range is a wave reduction).  Plain loads and dword stores: this runs once, not per step.
+__global__ __launch_bounds__(256) void pearson_encode_kernel(const float* const* __restrict__ members,
+                                                             uint32_t num_voxels, int cs,
+                                                             unsigned char* __restrict__ header,
+                                                             unsigned char* __restrict__ body,
+                                                             uint32_t* __restrict__ fallbacks) {
+    const int slots = pack_slots(cs);
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= (num_voxels + 63u) / 64u) return;
+    const int lane = int(threadIdx.x & 63u);
+    const uint32_t v = tile * 64u + uint32_t(lane);
+    // this lane's 16 B of run 0; dword k of run q is lane_words[256 q + k]
+    uint32_t* lane_words = reinterpret_cast<uint32_t*>(body + size_t(tile) * pack_tile_bytes(slots) + 16 * lane);
+    const int byte_run0 = pack_lo_runs(slots), code_run0 = byte_run0 + pack_byte_runs(slots);
+    uint32_t lo_w = 0, byte_w = 0, code_w = 0, fell_back = 0;
+#pragma unroll 1
+    for (int e = 0; e < slots; e++) {
+        const uint32_t bits = e < cs && v < num_voxels ? __float_as_uint(members[e][v]) : 0u;
+        const uint32_t ex = (bits >> 23) & 0xFFu;
+        uint32_t emin = ex != 0u ? ex : 256u, emax = ex;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            emin = min(emin, uint32_t(__shfl_xor(int(emin), o)));
+            emax = max(emax, uint32_t(__shfl_xor(int(emax), o)));
+        }
+        const uint32_t base = pack_segment_base(emin, emax, emax == 255u);
+        const uint32_t b = base == kPackFallback ? 0u : bits;  // a fallback segment's planes hold zeros
+        lo_w |= pack_lo16(b) << (16 * (e & 1));
+        byte_w |= pack_byte(b) << (8 * (e & 3));
+        code_w |= pack_code(b, base) << (4 * (e & 7));
+        if ((e & 1) == 1) {
+            lane_words[256 * (e / 8) + (e % 8) / 2] = lo_w;
+            lo_w = 0;
+        }
+        if ((e & 3) == 3) {
+            lane_words[256 * (byte_run0 + e / 16) + (e % 16) / 4] = byte_w;
+            byte_w = 0;
+        }
+        if ((e & 7) == 7) {
+            lane_words[256 * (code_run0 + e / 32) + (e % 32) / 8] = code_w;
+            code_w = 0;
+        }
+        if (lane == 0) header[size_t(tile) * size_t(slots) + size_t(e)] = static_cast<unsigned char>(base);
+        fell_back += base == kPackFallback ? 1u : 0u;  // (padded slots always fit)
+    }
+    if (slots % 32 == 16) {  // the unused half of the last code run
+        lane_words[256 * (code_run0 + slots / 32) + 2] = 0u;
+        lane_words[256 * (code_run0 + slots / 32) + 3] = 0u;
+    }
+    if (lane == 0 && fell_back != 0u) atomicAdd(fallbacks, fell_back);
+}
+
+hipError_t launch_pack_members(const float* const* d_members, int cs, size_t num_voxels, unsigned char* header,
+                               unsigned char* body, uint32_t* d_fallbacks, hipStream_t s) {
+    if (cs < kPackMinMembers || cs > kPackMaxMembers || num_voxels == 0 || num_voxels >= (size_t(1) << 32))
+        return hipErrorInvalidValue;
+    const size_t tiles = (num_voxels + 63) / 64;
+    hipLaunchKernelGGL(pearson_encode_kernel, dim3(unsigned((tiles + 3) / 4)), dim3(256), 0, s, d_members,
+                       uint32_t(num_voxels), cs, header, body, d_fallbacks);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -279,8 +472,6 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_reg_lds_kernel(const f
 //   PAD   cs lies in (G * S - PAD, G * S]: only the last PAD slots of the last group can be padding (they read 0, their
 //         deviation is forced to 0 and a_e = 0 for e >= cs: every pass adds +0 for them, as in pearson_reg_kernel).
 // ---------------------------------------------------------------------------------------------------------
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ float from_lane(float v, int src_lane) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
 }
@@ -719,11 +910,26 @@ void launch_reg(const float* const* d_members, const float* d_prep, float* d_out
     constexpr int kData = CS_PAD * VPT;
     constexpr int kMinWaves = kData <= 64 ? 4 : kData <= 128 ? 2 : kData <= 160 ? 1 : 2;
     if (cs == CS_PAD)
-        hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, true, kMinWaves>), dim3(unsigned(blocks)), dim3(256), 0, s,
-                           d_members, d_prep, d_out, uint32_t(num_voxels), cs);
+        hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, true, kMinWaves, false>), dim3(unsigned(blocks)), dim3(256),
+                           0, s, d_members, d_prep, d_out, uint32_t(num_voxels), cs, PackedMembers{});
     else
-        hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, false, kMinWaves>), dim3(unsigned(blocks)), dim3(256), 0,
-                           s, d_members, d_prep, d_out, uint32_t(num_voxels), cs);
+        hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, VPT, false, kMinWaves, false>), dim3(unsigned(blocks)),
+                           dim3(256), 0, s, d_members, d_prep, d_out, uint32_t(num_voxels), cs, PackedMembers{});
+}
+
+// the packed form: 17..128 members, one voxel per lane.  Up to 64 slots it is held to 96 VGPRs (five waves per SIMD,
+// as the raw 64-member kernel's 93).
+template <int CS_PAD>
+void launch_reg_packed(const float* const* d_members, const float* d_prep, float* d_out, size_t num_voxels, int cs,
+                       const PackedMembers& packed, hipStream_t s) {
+    constexpr int kMinWaves = CS_PAD <= 64 ? 5 : 2;
+    const unsigned blocks = unsigned((num_voxels + 255) / 256);
+    if (cs == CS_PAD)
+        hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, 1, true, kMinWaves, true>), dim3(blocks), dim3(256), 0, s,
+                           d_members, d_prep, d_out, uint32_t(num_voxels), cs, packed);
+    else
+        hipLaunchKernelGGL((pearson_reg_kernel<CS_PAD, 1, false, kMinWaves, true>), dim3(blocks), dim3(256), 0, s,
+                           d_members, d_prep, d_out, uint32_t(num_voxels), cs, packed);
 }
 
 template <int CS_PAD>
@@ -879,7 +1085,7 @@ hipError_t launch_pearson_symmetric(const float* const* d_members_ref, const flo
 
 hipError_t launch_pearson(const float* const* d_members, int cs, size_t num_voxels, int max_vpt, const RefSource& ref,
                           float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
-                          LaunchInfo* info) {
+                          LaunchInfo* info, const PackedMembers& packed) {
     if (cs == 1) {  // CorrelationCalculator.cpp:882-885
         if (!ref.run()) return hipSuccess;
         if (ev_begin) (void)hipEventRecord(ev_begin, s);
@@ -897,7 +1103,18 @@ hipError_t launch_pearson(const float* const* d_members, int cs, size_t num_voxe
     const char* name;
     hipError_t e = hipSuccess;
     if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    if (cs <= 224) {
+    if (packed.header && cs >= kPackMinMembers && cs <= kPackMaxMembers && num_voxels > 0) {
+        switch (pack_slots(cs)) {
+            case 32: launch_reg_packed<32>(d_members, d_prep, d_out, num_voxels, cs, packed, s); break;
+            case 48: launch_reg_packed<48>(d_members, d_prep, d_out, num_voxels, cs, packed, s); break;
+            case 64: launch_reg_packed<64>(d_members, d_prep, d_out, num_voxels, cs, packed, s); break;
+            case 80: launch_reg_packed<80>(d_members, d_prep, d_out, num_voxels, cs, packed, s); break;
+            case 96: launch_reg_packed<96>(d_members, d_prep, d_out, num_voxels, cs, packed, s); break;
+            case 112: launch_reg_packed<112>(d_members, d_prep, d_out, num_voxels, cs, packed, s); break;
+            default: launch_reg_packed<128>(d_members, d_prep, d_out, num_voxels, cs, packed, s); break;
+        }
+        name = "pearson_reg_kernel";
+    } else if (cs <= 224) {
         const int cs_pad = cs <= 8 ? 8 : cs <= 128 ? (cs + 15) / 16 * 16 : (cs + 31) / 32 * 32;
         // voxels per lane.  Measured on MI355X at 256^3 x 64 (profiles/): one voxel per lane (dword loads, 93 VGPRs,
         // 5 waves/SIMD) reaches 5.7 TB/s; 2 per lane (196 VGPRs, 2 waves/SIMD) 4.9 TB/s; 4 per lane 3.4 TB/s --

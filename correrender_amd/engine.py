@@ -31,6 +31,8 @@ class Measure(enum.IntEnum):
 # CORRELATION_MEASURE_TYPE_IDS (CorrelationDefines.hpp:54-57)
 MEASURE_IDS = ["pearson", "spearman", "kendall", "mi_binned", "mi_kraskov",
                "binned_mi_correlation_coefficient", "kmi_correlation_coefficient"]
+# crf_member_layout (include/corrfield.h)
+MEMBER_LAYOUTS = ["auto", "raw", "packed"]
 
 
 def default_kraskov_k(cs: int) -> int:
@@ -387,6 +389,18 @@ class CorrField:
 
     def last_kernel_name(self) -> str:
         return (self._lib.crf_last_kernel_name(self._ctx) or b"").decode()
+
+    def set_member_layout(self, mode: str):
+        """Member layout of the Pearson field: "auto" (default), "raw" or "packed" (include/corrfield.h)."""
+        self._check(self._lib.crf_set_member_layout(self._ctx, MEMBER_LAYOUTS.index(mode)))
+
+    def last_member_layout(self) -> str:
+        """"raw" or "packed": what the last Pearson field evaluation read."""
+        return MEMBER_LAYOUTS[self._lib.crf_last_member_layout(self._ctx)]
+
+    def members_changed(self):
+        """Call after writing into bound (borrowed) member tensors: drops every copy and cache derived from them."""
+        self._check(self._lib.crf_members_changed(self._ctx))
 
     def synth_box_member(self, out, xs, ys, zs_local, z_begin, zs_global, c, cs, seed, stream: int = 0):
         self._check(self._lib.crf_synth_box_member(self._ctx, C.c_void_p(out.data_ptr()), xs, ys, zs_local, z_begin,

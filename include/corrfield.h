@@ -317,6 +317,32 @@ int crf_tile_field_device(crf_context* ctx, const void* device_linear, void* dev
  * Host-only helper, no context needed; NaN for k < 1 or cs < 1. */
 double crf_max_mutual_information_kraskov(int k, int cs);
 
+/* ---- member layout of the Pearson field ---------------------------------------------------------------------------
+ * At 17..128 members the Pearson field can stream its members from a lossless packed copy in HBM (3.5 bytes per member
+ * SLOT, the member count rounded up to 16, + 1 byte per slot and 64 voxels: 225 B per voxel at 64 members instead of 256,
+ * but 112.5 B at 17 instead of 68; values whose 64-voxel segment does not fit the format are read from the members
+ * themselves), built on the compute stream at the first Pearson field evaluation after the members change.  Results are
+ * bit-identical.
+ *   AUTO    (default) packs when 17 <= cs <= 128, the copy moves at most 92.5 % of the bytes of the members per
+ *           evaluation (31-32, 48, 61-64, 79-80, 92-96, 109-112, 122-128 members), the grid has at least 2^20 voxels,
+ *           no more than 5 % of the member segments fall back, and at least max(8 GiB, 10 % of the device memory)
+ *           stays free; else RAW
+ *   RAW     never packs
+ *   PACKED  packs whenever the member count allows it (tests)
+ * The copy is dropped by crf_set_grid, crf_upload_members, crf_bind_members_device and crf_set_member_layout.  The
+ * library cannot see writes into BORROWED members (crf_bind_members_device): after changing their contents, call
+ * crf_members_changed (or bind them again) before the next evaluation.  crf_members_changed drops everything derived
+ * from the members (packed copy, cached extrema, pointer tables).  crf_last_member_layout: the layout the last Pearson
+ * field evaluation read (CRF_MEMBER_LAYOUT_RAW or CRF_MEMBER_LAYOUT_PACKED). */
+typedef enum crf_member_layout {
+    CRF_MEMBER_LAYOUT_AUTO = 0,
+    CRF_MEMBER_LAYOUT_RAW = 1,
+    CRF_MEMBER_LAYOUT_PACKED = 2
+} crf_member_layout;
+int crf_set_member_layout(crf_context* ctx, int mode);
+int crf_last_member_layout(const crf_context* ctx);
+int crf_members_changed(crf_context* ctx);
+
 /* ---- instrumentation --------------------------------------------------------------------------------------- */
 /* When enabled, every crf_compute* brackets its dominant (per-voxel) kernel with HIP events on the launch stream. */
 int crf_set_profiling(crf_context* ctx, int enabled);
