@@ -40,10 +40,6 @@ std::string fmt(const char* f, ...) {
     va_end(ap);
     return buf;
 }
-}  // namespace
-
-
-namespace {
 
 int fail(crf_context* c, int code, const std::string& msg) {
     if (c) c->err = msg;
@@ -220,6 +216,535 @@ hipEvent_t take_event(crf_context* c) {
     hipEvent_t e = nullptr;
     if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
+}
+
+hipStream_t stream_of(crf_context* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
+
+// a launcher's hipError_t as the ABI status
+int launch_status(crf_context* c, hipError_t e) {
+    if (e == hipSuccess) return CRF_OK;
+    return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
+}
+
+// One timed launch.  Takes an event pair when profiling is on, for the launcher to record around its per-voxel kernel;
+// finish() names the kernel for crf_last_kernel_name, queues the pair for crf_take_kernel_time and maps the launcher's
+// hipError_t to the ABI status.
+struct TimedLaunch {
+    crf_context* c;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    crf::LaunchInfo info;
+    explicit TimedLaunch(crf_context* ctx, bool timed = true) : c(ctx) {
+        if (c->profiling && timed) {
+            e0 = take_event(c);
+            e1 = take_event(c);
+        }
+    }
+    int finish(hipError_t e) {
+        c->last_kernel = info.kernel_name ? info.kernel_name : "";
+        if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
+        return launch_status(c, e);
+    }
+};
+
+// The only place that validates a crf_params.  member_limit: the most members the mode's kernels take (0: any number);
+// who: the mode as the member-limit message names it (null: field mode, which names the measure).
+int check_params(crf_context* c, const crf_params* p, int member_limit, const char* who = nullptr) {
+    if (!p) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (p->measure < CRF_PEARSON || p->measure > CRF_KMI_CC)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("unknown measure %d", p->measure));
+    for (int v : p->reserved)
+        if (v != 0) return fail(c, CRF_ERR_ARGUMENT, "crf_params.reserved must be zero");
+    if (member_limit > 0 && c->cs > member_limit)
+        return fail(c, CRF_ERR_UNSUPPORTED,
+                    who ? fmt("%s at most %d members", who, member_limit)
+                        : fmt("measure %d supports at most %d members (got %d)", p->measure, member_limit, c->cs));
+    if ((p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC) && (p->num_bins < 1 || p->num_bins > 255))
+        return fail(c, CRF_ERR_ARGUMENT, fmt("num_bins %d outside [1,255]", p->num_bins));
+    // any k >= 1, like the reference (its k+1-nearest-neighbour query returns at most cs points; psi(k) itself is used)
+    if ((p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) && p->k < 1)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be at least 1", p->k));
+    return CRF_OK;
+}
+
+// prepared slots [first, first + count); one: the call takes the single slot `first` and says so
+int check_slots(crf_context* c, int first, int count, bool one = false) {
+    if (count >= 0 && first >= 0 && first + count <= CRF_PREPARED_SLOTS) return CRF_OK;
+    return fail(c, CRF_ERR_ARGUMENT,
+                one ? fmt("slot %d outside [0,%d)", first, CRF_PREPARED_SLOTS)
+                    : fmt("slots [%d, %d) outside [0, %d)", first, first + count, CRF_PREPARED_SLOTS));
+}
+
+int install_secondary_table(crf_context* c) {
+    if (!c->d_sec_table)
+        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_sec_table), sizeof(float*) * size_t(c->cs)));
+    CRF_HIP(c, hipMemcpyAsync(c->d_sec_table, c->sec_members.data(), sizeof(float*) * size_t(c->cs),
+                              hipMemcpyHostToDevice, c->stream));
+    CRF_HIP(c, hipStreamSynchronize(c->stream));
+    c->sec_minmax_valid = false;
+    c->windows = 0;
+    return CRF_OK;
+}
+
+int ensure_workspace(crf_context* c, size_t need) {
+    if (need > c->workspace_bytes) {
+        CRF_HIP(c, hipDeviceSynchronize());  // an earlier evaluation on a caller stream may still use the old workspace
+        if (c->d_workspace) (void)hipFree(c->d_workspace);
+        c->d_workspace = nullptr;
+        c->workspace_bytes = 0;
+        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_workspace), need));
+        c->workspace_bytes = need;
+    }
+    return CRF_OK;
+}
+
+// Lazy scratch of the whole local grid.  num_voxels == alloc_voxels whenever no NarrowScope is active (crf_set_grid sets
+// both, nothing else writes them), so every size is taken from alloc_voxels.
+int ensure_todo(crf_context* c) {  // the sort-based rank kernels' list of deferred voxels
+    if (!c->d_todo) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_todo), (c->alloc_voxels + 1) * sizeof(uint32_t)));
+    return CRF_OK;
+}
+
+int ensure_out(crf_context* c) {  // device result of the host-output calls
+    if (!c->d_out) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), c->alloc_voxels * sizeof(float)));
+    return CRF_OK;
+}
+
+// ---- member volumes of 4 GiB and more: evaluation in windows ----------------------------------------------------------
+constexpr size_t kWindowVoxels = size_t(1) << 29;  // 2 GiB of every member per launch
+
+int ensure_windows(crf_context* c) {
+    if (c->windows > 0) return CRF_OK;
+    const int windows = int((c->alloc_voxels + kWindowVoxels - 1) / kWindowVoxels);
+    const bool sec = !c->sec_members.empty();
+    std::vector<const float*> table(size_t(windows) * size_t(c->cs) * (sec ? 2 : 1));
+    for (int w = 0; w < windows; w++)
+        for (int m = 0; m < c->cs; m++) {
+            table[(size_t(w) * (sec ? 2 : 1)) * size_t(c->cs) + size_t(m)] = c->members[size_t(m)] + size_t(w) * kWindowVoxels;
+            if (sec) table[(size_t(w) * 2 + 1) * size_t(c->cs) + size_t(m)] = c->sec_members[size_t(m)] + size_t(w) * kWindowVoxels;
+        }
+    if (c->d_window_tables) (void)hipFree(c->d_window_tables);
+    c->d_window_tables = nullptr;
+    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_window_tables), table.size() * sizeof(float*)));
+    CRF_HIP(c, hipMemcpy(c->d_window_tables, table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
+    c->windows = windows;
+    c->window_has_secondary = sec;
+    return CRF_OK;
+}
+
+// narrows the context to one window of a >= 4 GiB grid, or to one voxel range of a host-output evaluation, for the
+// duration of a launch; restores it on every exit path
+struct NarrowScope {
+    crf_context* c;
+    const float** table;
+    const float** sec_table;
+    size_t voxels;
+    int vpt;
+    explicit NarrowScope(crf_context* ctx)
+        : c(ctx), table(ctx->d_member_table), sec_table(ctx->d_sec_table), voxels(ctx->num_voxels), vpt(ctx->max_vpt) {}
+    size_t select_window(int w) {  // returns the window's first voxel
+        const size_t per = size_t(c->window_has_secondary ? 2 : 1) * size_t(c->cs);
+        c->d_member_table = c->d_window_tables + size_t(w) * per;
+        if (c->window_has_secondary) c->d_sec_table = c->d_window_tables + size_t(w) * per + size_t(c->cs);
+        c->num_voxels = std::min(kWindowVoxels, c->alloc_voxels - size_t(w) * kWindowVoxels);
+        return size_t(w) * kWindowVoxels;
+    }
+    void select_range(int j) {  // range j of ensure_host_ranges
+        c->d_member_table = c->d_chunk_tables + size_t(j) * size_t(c->cs);
+        c->num_voxels = c->chunk_first[j + 1] - c->chunk_first[j];
+    }
+    ~NarrowScope() {
+        c->d_member_table = table;
+        c->d_sec_table = sec_table;
+        c->num_voxels = voxels;
+        c->max_vpt = vpt;
+    }
+};
+
+// runs launch(out + first voxel of the window) for every window of a >= 4 GiB grid, or once for an ordinary grid
+template <class Launch>
+int for_each_window(crf_context* c, float* out, Launch&& launch) {
+    if (!c->windowed) return launch(out);
+    if (int r = ensure_windows(c)) return r;
+    NarrowScope scope(c);
+    for (int w = 0; w < c->windows; w++) {
+        const size_t first = scope.select_window(w);
+        if (int r = launch(out + first)) return r;
+    }
+    return CRF_OK;
+}
+
+// CRF_FLAG_SYMMETRIC: measure(primary members at v, secondary members at v) for every voxel v
+int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream_t s) {
+    TimedLaunch launch(c);
+    if (launch.e0) (void)hipEventRecord(launch.e0, s);
+    const char*& kernel = launch.info.kernel_name;
+    hipError_t e = hipErrorNotSupported;
+    if (p->measure == CRF_PEARSON) {
+        e = crf::launch_pearson_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, out, s);
+        kernel = "pearson_symmetric_kernel";
+    } else if (p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) {
+        e = crf::launch_mi_kraskov_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->k,
+                                             kraskov_c_term(p->k, 1), p->measure == CRF_KMI_CC, c->d_tables, out, s);
+        kernel = "kraskov_direct_kernel";
+    } else {  // Spearman, Kendall, the binned measures: sort-based where it applies, else the any-member-count kernel
+        const char* force_direct = getenv("CRF_SYMMETRIC_DIRECT");  // tuning / tests: the any-member-count kernel
+        if (!(force_direct && *force_direct == '1')) {
+            e = crf::launch_sorted_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->measure,
+                                             p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables,
+                                             out, s);
+            kernel = "sorted_symmetric_kernel";
+        }
+        if (e == hipErrorNotSupported) {
+            if (int r = ensure_workspace(c, crf::direct_symmetric_workspace_bytes(c->cs, c->num_voxels, p->measure))) return r;
+            e = crf::launch_direct_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->measure, p->num_bins,
+                                             p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables, c->d_workspace,
+                                             out, s);
+            kernel = "direct_symmetric_kernel";
+        }
+    }
+    if (e == hipErrorNotSupported) {
+        if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, c->num_voxels))) return r;
+        const crf::PairArgs a{p->measure, p->num_bins, p->k, 0, 1, p->min_ref, p->max_ref, p->min_query, p->max_query,
+                              kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
+        e = crf::launch_pair_requests(c->d_member_table, c->d_sec_table, c->cs, c->xs, c->ys, c->num_voxels, nullptr,
+                                      c->num_voxels, a, c->d_tables, c->d_workspace, out, s);
+        kernel = "pair_request_kernel";
+    }
+    if (launch.e0 && launch.e1) (void)hipEventRecord(launch.e1, s);
+    return launch.finish(e);
+}
+
+int ref_voxel(crf_context* c, int x, int y, int z, size_t* voxel) {
+    if (x < 0 || y < 0 || z < 0 || x >= c->xs || y >= c->ys || z >= c->zs)
+        return fail(c, CRF_ERR_ARGUMENT,
+                    fmt("reference point (%d,%d,%d) outside the local grid %dx%dx%d", x, y, z, c->xs, c->ys, c->zs));
+    *voxel = (size_t(z) * size_t(c->ys) + size_t(y)) * size_t(c->xs) + size_t(x);  // IDXS, DataSet.hpp:37
+    return CRF_OK;
+}
+
+// ---- device result -> the caller's (pageable) host buffer -------------------------------------------------------------
+// The caller of calculateCpu owns a freshly allocated `new float[xs*ys*zs]` (VolumeData.cpp:1222-1226): pageable and never
+// touched.  Measured on MI355X hosts at 256^3 (67 MB, profiles/r03_host_boundary.md): one DMA into pinned memory 1.19 ms
+// (56.5 GB/s, the PCIe floor); a kernel storing straight into device-mapped pinned memory 1.22 ms; 8 host threads move
+// pinned -> resident pageable memory at 120 GB/s but only at 14 GB/s into never-touched pages (first-touch faults).
+//
+// So a host-output evaluation is a pipeline over a few voxel RANGES (ensure_host_ranges):
+//   GPU     the per-voxel kernel of each range stores its results straight into a pinned, device-mapped staging buffer
+//           (no device-side result buffer, no DMA engine: the stores cross PCIe while the kernel runs -- the kernel is
+//           simply throttled to the link rate, which is the floor anyway);
+//   host    a persistent pool of copier threads (crf_pool.h) moves each finished range from the staging buffer into
+//           the caller's buffer, and while it waits for a range it faults the destination pages of the ranges ahead in
+//           (MADV_POPULATE_WRITE batches the faults; transparent huge pages are requested for the buffer first).
+// Range sizes are staggered over two streams so that kernel ends alternate and the last copy is small (ensure_host_ranges).
+// CRF_HOST_PATH=dma keeps results in HBM and copies each range with the DMA engine instead (also used when a post-pass
+// has to read the result back: CRF_FLAG_ABSOLUTE_VALUE).
+constexpr int kMadvPopulateWrite = 23;  // MADV_POPULATE_WRITE (Linux 5.14), not in every libc header
+constexpr size_t kPage = 4096;
+
+int env_int_or(const char* name, int fallback) {
+    const char* v = getenv(name);
+    return (v && *v) ? atoi(v) : fallback;
+}
+
+// faults [lo, hi) of the caller's buffer in (write access); mode 0: leave it to the copy, 1: touch, 2: populate
+void fault_in(char* base, size_t lo, size_t hi, int mode) {
+    if (mode == 0 || lo >= hi) return;
+    const uintptr_t a = (reinterpret_cast<uintptr_t>(base) + lo) & ~(kPage - 1);
+    const uintptr_t e = (reinterpret_cast<uintptr_t>(base) + hi + kPage - 1) & ~(kPage - 1);
+    if (mode == 2 && madvise(reinterpret_cast<void*>(a), e - a, kMadvPopulateWrite) == 0) return;
+    // fallback / mode 1: one write per page.  The bytes written are inside the caller's buffer and are overwritten by
+    // the result afterwards.
+    for (size_t off = lo; off < hi; off += kPage) static_cast<volatile char*>(base)[off] = 0;
+    static_cast<volatile char*>(base)[hi - 1] = 0;
+}
+
+// thread w's share of byte range [r_lo, r_hi) among `workers` threads, split on page boundaries
+void thread_share(size_t r_lo, size_t r_hi, int w, int workers, size_t* lo, size_t* hi) {
+    const size_t per = (((r_hi - r_lo) + size_t(workers) - 1) / size_t(workers) + kPage - 1) & ~(kPage - 1);
+    *lo = std::min(r_hi, r_lo + size_t(w) * per);
+    *hi = std::min(r_hi, *lo + per);
+}
+
+int ensure_copy_pool(crf_context* c) {
+    if (c->copy_pool) return CRF_OK;
+    const unsigned hw = std::thread::hardware_concurrency();
+    int cap = int(std::min<unsigned>(16u, std::max(1u, hw / 2)));
+    if (c->copy_threads_cap > 0) cap = std::min(cap, c->copy_threads_cap);
+    const int forced = env_int_or("CRF_COPY_THREADS", 0);
+    if (forced >= 1) cap = std::min(forced, 64);
+    // copier threads idle-spin for a short while only: back-to-back evaluations hand over within ~0.1 ms
+    c->copy_pool = std::make_unique<crf::SpinPool>(cap, nullptr, 300e-6);
+    c->copy_threads = cap;
+    if (forced >= 1 || cap <= 2) return CRF_OK;
+    // one-off calibration: how many of the pool's threads move pinned -> pageable memory fastest on this host
+    const size_t bytes = std::min<size_t>(c->alloc_voxels * sizeof(float), size_t(16) << 20);
+    std::vector<char> dst(bytes, 1);
+    const char* src = reinterpret_cast<const char*>(c->h_staging);
+    double best = 1e30;
+    for (int t : {2, 4, 8, 12, 16}) {
+        if (t > cap) break;
+        double fastest = 1e30;
+        for (int rep = 0; rep < 3; rep++) {
+            const auto t0 = std::chrono::steady_clock::now();
+            c->copy_pool->run([&](int w) -> int {
+                if (w >= t) return 0;
+                size_t lo, hi;
+                thread_share(0, bytes, w, t, &lo, &hi);
+                if (lo < hi) memcpy(dst.data() + lo, src + lo, hi - lo);
+                return 0;
+            });
+            fastest = std::min(fastest, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        }
+        if (fastest < best * 0.93) {  // more threads only for a real gain
+            best = fastest;
+            c->copy_threads = t;
+        }
+    }
+    return CRF_OK;
+}
+
+// Plain form for small results and the sibling reductions: kernel into HBM, one copy.
+int copy_result_to_host(crf_context* c, const float* d_src, float* host_out, size_t count) {
+    CRF_HIP(c, hipMemcpyAsync(host_out, d_src, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    CRF_HIP(c, hipStreamSynchronize(c->stream));
+    return CRF_OK;
+}
+
+// One evaluation of the field or symmetric mode on the context as it is narrowed right now.
+// phase: bit 0 = reference-side preparation, bit 1 = per-voxel kernel (crf_internal.h RefSource::phase);
+// slot < 0: the context's own preparation buffer
+int compute_impl_one(crf_context* c, const crf_params* p, const void* device_reference_values, void* device_out,
+                     void* stream, unsigned phase, int slot, const crf::RefOverride* ov) {
+    if (int r = check_ready(c)) return r;
+    const bool symmetric = p && (p->flags & CRF_FLAG_SYMMETRIC);
+    const bool any_member_count = p && p->measure == CRF_PEARSON && !symmetric;  // the Pearson field kernel
+    if (int r = check_params(c, p, any_member_count ? 0 : crf::kMaxGenericMembers,
+                             symmetric ? "the symmetric mode supports" : nullptr))
+        return r;
+    if (!device_out && (phase & 2u)) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (int r = bind_device(c)) return r;
+    hipStream_t s = stream_of(c, stream);
+    float* out = static_cast<float*>(device_out);
+    if (symmetric) {
+        if (phase != 3u) return fail(c, CRF_ERR_ARGUMENT, "the symmetric mode has no reference-side preparation");
+        if (c->sec_members.empty())
+            return fail(c, CRF_ERR_STATE, "CRF_FLAG_SYMMETRIC needs secondary members (crf_upload_secondary_members)");
+        return for_each_window(c, out, [&](float* o) { return compute_symmetric(c, p, o, s); });
+    }
+    float* prep = c->d_prep;
+    if (slot >= 0) {
+        if (!c->d_prep_slots)
+            CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_prep_slots), size_t(CRF_PREPARED_SLOTS) * crf::kPrepBytes));
+        prep = c->d_prep_slots + size_t(slot) * (crf::kPrepBytes / sizeof(float));
+    }
+
+    // 1. reference vector (CorrelationCalculator.cpp:802-818): a device array, a host array (copied stream-ordered),
+    //    or the reference point -- then the gather is fused into the estimator's preparation kernel.
+    crf::RefSource ref{static_cast<const float*>(device_reference_values), 0};
+    ref.phase = phase;
+    if (!(phase & 1u)) {
+        ref.values = nullptr;  // prepared earlier: no reference vector is read
+    } else if (!ref.values && ov) {
+        // crf_group, direct exchange: the preparation kernel reads the values out of another context's members
+        ref.table = ov->table;
+        ref.voxel = ov->voxel;
+    } else if (!ref.values && (p->flags & CRF_FLAG_REFERENCE_FROM_SECONDARY)) {
+        if (c->sec_members.empty())
+            return fail(c, CRF_ERR_STATE, "CRF_FLAG_REFERENCE_FROM_SECONDARY needs secondary members");
+        size_t voxel;
+        if (int r = ref_voxel(c, p->ref_x, p->ref_y, p->ref_z, &voxel)) return r;
+        CRF_HIP(c, crf::launch_gather_reference(c->d_sec_table, c->cs, voxel, c->d_ref, s));
+        ref.values = c->d_ref;
+    }
+    if ((phase & 1u) && !ref.values && !ref.table) {
+        if (p->reference_values) {
+            CRF_HIP(c, hipMemcpyAsync(c->d_ref, p->reference_values, sizeof(float) * size_t(c->cs),
+                                      hipMemcpyHostToDevice, s));
+            ref.values = c->d_ref;
+        } else {
+            if (int r = ref_voxel(c, p->ref_x, p->ref_y, p->ref_z, &ref.voxel)) return r;
+        }
+    }
+
+    // 2. estimator
+    TimedLaunch launch(c, phase & 2u);
+    const hipEvent_t e0 = launch.e0, e1 = launch.e1;
+    crf::LaunchInfo* info = &launch.info;
+    const bool binned = p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC;
+    const bool kraskov = p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC;
+    const int est = p->kraskov_estimator_index == 2 ? 2 : 1;  // clamp as CorrelationCalculator.cpp:765
+    const crf::BinnedArgs ba{p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query,
+                             p->measure == CRF_BINNED_MI_CC};
+    hipError_t e = hipErrorNotSupported;
+    if (p->measure != CRF_PEARSON && c->cs > crf::kMaxSortMembers) {
+        // any-member-count path: a specialised kernel where one applies, else kernels_generic.hip
+        if (binned) {  // O(cs) histogram kernel, unless there are too many bins for the LDS rows
+            e = crf::launch_mi_binned_hist(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s, e0,
+                                           e1, info);
+        } else if (kraskov) {  // tile-free single-sweep top-K kernel, unless k > 128 or the tables are beyond LDS
+            const crf::KraskovArgs ka{p->k, est, p->measure == CRF_KMI_CC, kraskov_c_term(p->k, est)};
+            e = crf::launch_mi_kraskov_direct(c->d_member_table, c->cs, c->num_voxels, ref, ka, c->d_tables, prep, out, s,
+                                              e0, e1, info);
+        }
+        if (e == hipErrorNotSupported) {  // the O(cs^2) counting / repeated-minimum kernels
+            if (int r = ensure_workspace(c, crf::generic_workspace_bytes(c->cs, c->num_voxels))) return r;
+            const crf::GenericArgs ga{p->measure, p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, p->k,
+                                      est, kraskov_c_term(p->k > 0 ? p->k : 1, est)};
+            const bool rank_measure = p->measure == CRF_SPEARMAN || p->measure == CRF_KENDALL;
+            if (rank_measure && c->cs <= 256)
+                if (int r = ensure_todo(c)) return r;
+            e = crf::launch_generic(c->d_member_table, c->cs, c->num_voxels, ref, ga, c->d_tables, prep, c->d_workspace,
+                                    out, s, e0, e1, info, rank_measure ? c->d_todo : nullptr);
+        }
+        return launch.finish(e);
+    }
+    switch (p->measure) {
+        case CRF_PEARSON: {
+            crf::PackedMembers packed;
+            if (phase & 2u)
+                if (int r = ensure_packed(c, s, &packed)) return r;
+            e = crf::launch_pearson(c->d_member_table, c->cs, c->num_voxels, std::min(c->max_vpt, alignment_vpt(out)), ref,
+                                    prep, out, s, e0, e1, info, packed);
+            if (phase & 2u) c->last_layout = packed.header ? CRF_MEMBER_LAYOUT_PACKED : CRF_MEMBER_LAYOUT_RAW;
+            break;
+        }
+        case CRF_SPEARMAN:
+        case CRF_KENDALL:
+            if (c->cs > 16)
+                if (int r = ensure_todo(c)) return r;
+            e = (p->measure == CRF_SPEARMAN ? crf::launch_spearman : crf::launch_kendall)(
+                c->d_member_table, c->cs, c->num_voxels, ref, prep, c->d_todo, out, s, e0, e1, info);
+            break;
+        case CRF_MI_BINNED:
+        case CRF_BINNED_MI_CC:
+            if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1')  // tuning: histogram kernel for any cs
+                e = crf::launch_mi_binned_hist(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s,
+                                               e0, e1, info);
+            if (e == hipErrorNotSupported)
+                e = crf::launch_mi_binned(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s,
+                                          e0, e1, info);
+            break;
+        case CRF_MI_KRASKOV:
+        case CRF_KMI_CC: {
+            const crf::KraskovArgs ka{p->k, est, p->measure == CRF_KMI_CC, kraskov_c_term(p->k, est)};
+            e = crf::launch_mi_kraskov(c->d_member_table, c->cs, c->num_voxels, ref, ka, c->d_tables, prep, out, s,
+                                       e0, e1, info);
+            break;
+        }
+    }
+    const int rc = launch.finish(e);
+    if (e == hipErrorNotSupported)
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("measure %d is not implemented by this build", p->measure));
+    return rc;
+}
+
+// An ordinary grid: one call.  A grid whose members are 4 GiB or larger: the reference side once, from the whole grid
+// (the reference point indexes it with 64 bits), then the per-voxel kernel window by window.
+int compute_impl(crf_context* c, const crf_params* p, const void* device_reference_values, void* device_out,
+                 void* stream, unsigned phase, int slot, const crf::RefOverride* ov = nullptr) {
+    if (!c || !c->windowed || !p || (p->flags & CRF_FLAG_SYMMETRIC))
+        return compute_impl_one(c, p, device_reference_values, device_out, stream, phase, slot, ov);
+    if (phase & 1u)
+        if (int r = compute_impl_one(c, p, device_reference_values, nullptr, stream, 1u, slot, ov)) return r;
+    if (!(phase & 2u)) return CRF_OK;
+    if (!device_out) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    return for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
+        return compute_impl_one(c, p, nullptr, o, stream, 2u, slot, nullptr);
+    });
+}
+
+// CRF_FLAG_ABSOLUTE_VALUE after a device evaluation (opt-in: what the reference's accelerator paths do)
+int apply_abs(crf_context* c, const crf_params* p, void* device_out, void* stream) {
+    if (p->flags & CRF_FLAG_ABSOLUTE_VALUE)
+        CRF_HIP(c, crf::launch_abs(static_cast<float*>(device_out), c->num_voxels, stream_of(c, stream)));
+    return CRF_OK;
+}
+
+// The voxel ranges of a host-output evaluation: one member-pointer table per range (pointers advanced by the range's
+// first voxel), so that every per-voxel kernel can be launched on a range without knowing about ranges.  Range lengths
+// are multiples of 1024 voxels (4 KiB: every range stays as aligned as the members themselves) and shrink towards the
+// end: the copy of the last range into the caller's buffer is the only host work no kernel hides.
+int ensure_host_ranges(crf_context* c) {
+    if (c->host_chunks > 0) return CRF_OK;
+    const size_t n = c->alloc_voxels;
+    std::vector<size_t> first{0};
+    const int forced = env_int_or("CRF_HOST_CHUNKS", 0);
+    if (forced >= 1) {  // experiments: equal ranges
+        size_t per = (n + size_t(forced) - 1) / size_t(forced);
+        per = (per + 1023) & ~size_t(1023);
+        for (size_t at = per; at < n && int(first.size()) < kMaxHostChunks; at += per) first.push_back(at);
+    } else {
+        // Shares of 64, consecutive ranges alternating between two streams: 3 6 6 6 6 6 6 6 6 5 4 2 2.  The two streams'
+        // kernels run concurrently and share the link; with the FIRST range half the size of the others the kernel ends
+        // alternate (B0 A0 B1 A1 ...), so results land every ~1/11 of the run from early on, the copier threads always
+        // have a landed range to move, and the last ranges are small: only their copy is not hidden behind a kernel.
+        // Same-process A/B at 256^3 (tools/measure_host_path.py ab, profiles/r03_host_boundary_variants.txt), resident /
+        // fresh destination: 13 ranges 1.326 / 1.391 ms; 11 ranges (4 8x6 6 3 2 1) 1.336 / 1.452; 8 staggered ranges
+        // 1.369 / 1.467; 8 shrinking ranges 16 14 11 8 6 4 3 2 (pairs end together) 1.378 / 1.527; 8 equal 1.450 / 1.644.
+        std::vector<int> kShares = {3, 6, 6, 6, 6, 6, 6, 6, 6, 5, 4, 2, 2};
+        if (const char* e = getenv("CRF_HOST_SHARES")) {  // experiments: comma-separated shares of 64
+            std::vector<int> v;
+            int sum = 0;
+            for (const char* q = e; *q;) {
+                v.push_back(atoi(q));
+                sum += v.back();
+                while (*q && *q != ',') q++;
+                if (*q == ',') q++;
+            }
+            if (sum == 64 && v.size() >= 1 && v.size() <= size_t(kMaxHostChunks)) kShares = v;
+        }
+        size_t acc = 0;
+        for (int j = 0; j + 1 < int(kShares.size()); j++) {
+            acc += size_t(kShares[size_t(j)]);
+            const size_t at = (n / 64 * acc + 1023) & ~size_t(1023);
+            if (at > first.back() && at < n) first.push_back(at);
+        }
+    }
+    const int ranges = int(first.size());
+    first.push_back(n);
+    std::vector<const float*> table(size_t(ranges) * size_t(c->cs));
+    for (int j = 0; j < ranges; j++)
+        for (int m = 0; m < c->cs; m++) table[size_t(j) * size_t(c->cs) + size_t(m)] = c->members[size_t(m)] + first[size_t(j)];
+    if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
+    c->d_chunk_tables = nullptr;
+    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_chunk_tables), table.size() * sizeof(float*)));
+    CRF_HIP(c, hipMemcpy(c->d_chunk_tables, table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
+    if (!c->copy_stream) CRF_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int j = 0; j < ranges; j++)
+        if (!c->chunk_done[j]) CRF_HIP(c, hipEventCreateWithFlags(&c->chunk_done[j], hipEventDisableTiming));
+    for (int j = 0; j < ranges; j++)
+        if (!c->chunk_copied[j]) CRF_HIP(c, hipEventCreateWithFlags(&c->chunk_copied[j], hipEventDisableTiming));
+    if (!c->prep_done) CRF_HIP(c, hipEventCreateWithFlags(&c->prep_done, hipEventDisableTiming));
+    for (int j = 0; j <= ranges; j++) c->chunk_first[j] = first[size_t(j)];
+    c->host_chunks = ranges;
+    return CRF_OK;
+}
+
+// The ensemble-stat, set-predicate and DKL device calls: launch(out, stream, timed launch) once, or once per window of
+// a >= 4 GiB grid (stopping at the first window that fails), as one timed launch.
+template <class Launch>
+int run_windowed(crf_context* c, void* device_out, void* stream, Launch&& launch) {
+    if (int r = bind_device(c)) return r;
+    hipStream_t s = stream_of(c, stream);
+    TimedLaunch timed(c);
+    hipError_t e = hipSuccess;
+    const int rc = for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
+        e = launch(o, s, timed);
+        return e == hipSuccess ? CRF_OK : CRF_ERR_DEVICE;
+    });
+    if (int r = timed.finish(e)) return r;
+    return rc;  // not CRF_OK: the window tables could not be built
+}
+
+// ... and their host forms: device_call(device buffer) into the context's result buffer, one copy
+template <class DeviceCall>
+int to_host(crf_context* c, float* host_out, DeviceCall&& device_call) {
+    if (int r = check_ready(c)) return r;
+    if (!host_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
+    if (int r = bind_device(c)) return r;
+    if (int r = ensure_out(c)) return r;
+    if (int r = device_call(c->d_out)) return r;
+    return copy_result_to_host(c, c->d_out, host_out, c->alloc_voxels);
 }
 
 }  // namespace
@@ -446,17 +971,6 @@ int crf_member_minmax_divergent(crf_context* c, int secondary, float* out_min, f
     return CRF_OK;
 }
 
-static int install_secondary_table(crf_context* c) {
-    if (!c->d_sec_table)
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_sec_table), sizeof(float*) * size_t(c->cs)));
-    CRF_HIP(c, hipMemcpyAsync(c->d_sec_table, c->sec_members.data(), sizeof(float*) * size_t(c->cs),
-                              hipMemcpyHostToDevice, c->stream));
-    CRF_HIP(c, hipStreamSynchronize(c->stream));
-    c->sec_minmax_valid = false;
-    c->windows = 0;
-    return CRF_OK;
-}
-
 int crf_upload_secondary_members(crf_context* c, const float* const* host_members) {
     if (!c || !host_members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
     if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
@@ -507,154 +1021,13 @@ int crf_secondary_member_minmax(crf_context* c, float* out_min, float* out_max) 
     return CRF_OK;
 }
 
-static int ensure_workspace(crf_context* c, size_t need) {
-    if (need > c->workspace_bytes) {
-        CRF_HIP(c, hipDeviceSynchronize());  // an earlier evaluation on a caller stream may still use the old workspace
-        if (c->d_workspace) (void)hipFree(c->d_workspace);
-        c->d_workspace = nullptr;
-        c->workspace_bytes = 0;
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_workspace), need));
-        c->workspace_bytes = need;
-    }
-    return CRF_OK;
-}
-
-}  // extern "C"
-
-// ---- member volumes of 4 GiB and more: evaluation in windows ----------------------------------------------------------
-constexpr size_t kWindowVoxels = size_t(1) << 29;  // 2 GiB of every member per launch
-
-static int ensure_windows(crf_context* c) {
-    if (c->windows > 0) return CRF_OK;
-    const int windows = int((c->alloc_voxels + kWindowVoxels - 1) / kWindowVoxels);
-    const bool sec = !c->sec_members.empty();
-    std::vector<const float*> table(size_t(windows) * size_t(c->cs) * (sec ? 2 : 1));
-    for (int w = 0; w < windows; w++)
-        for (int m = 0; m < c->cs; m++) {
-            table[(size_t(w) * (sec ? 2 : 1)) * size_t(c->cs) + size_t(m)] = c->members[size_t(m)] + size_t(w) * kWindowVoxels;
-            if (sec) table[(size_t(w) * 2 + 1) * size_t(c->cs) + size_t(m)] = c->sec_members[size_t(m)] + size_t(w) * kWindowVoxels;
-        }
-    if (c->d_window_tables) (void)hipFree(c->d_window_tables);
-    c->d_window_tables = nullptr;
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_window_tables), table.size() * sizeof(float*)));
-    CRF_HIP(c, hipMemcpy(c->d_window_tables, table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
-    c->windows = windows;
-    c->window_has_secondary = sec;
-    return CRF_OK;
-}
-
-// narrows the context to one window for the duration of a launch; restores it on every exit path
-struct WindowScope {
-    crf_context* c;
-    const float** table;
-    const float** sec_table;
-    size_t voxels;
-    explicit WindowScope(crf_context* ctx) : c(ctx), table(ctx->d_member_table), sec_table(ctx->d_sec_table), voxels(ctx->num_voxels) {}
-    size_t select(int w) {  // returns the window's first voxel
-        const size_t per = size_t(c->window_has_secondary ? 2 : 1) * size_t(c->cs);
-        c->d_member_table = c->d_window_tables + size_t(w) * per;
-        if (c->window_has_secondary) c->d_sec_table = c->d_window_tables + size_t(w) * per + size_t(c->cs);
-        c->num_voxels = std::min(kWindowVoxels, c->alloc_voxels - size_t(w) * kWindowVoxels);
-        return size_t(w) * kWindowVoxels;
-    }
-    ~WindowScope() {
-        c->d_member_table = table;
-        c->d_sec_table = sec_table;
-        c->num_voxels = voxels;
-    }
-};
-
-// runs launch(out + first voxel of the window) for every window of a >= 4 GiB grid, or once for an ordinary grid
-template <class Launch>
-static int for_each_window(crf_context* c, float* out, Launch&& launch) {
-    if (!c->windowed) return launch(out);
-    if (int r = ensure_windows(c)) return r;
-    WindowScope scope(c);
-    for (int w = 0; w < c->windows; w++) {
-        const size_t first = scope.select(w);
-        if (int r = launch(out + first)) return r;
-    }
-    return CRF_OK;
-}
-
-extern "C" {
-
-// CRF_FLAG_SYMMETRIC: measure(primary members at v, secondary members at v) for every voxel v
-static int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream_t s) {
-    if (c->sec_members.empty())
-        return fail(c, CRF_ERR_STATE, "CRF_FLAG_SYMMETRIC needs secondary members (crf_upload_secondary_members)");
-    if (c->cs > crf::kMaxGenericMembers)
-        return fail(c, CRF_ERR_UNSUPPORTED, fmt("the symmetric mode supports at most %d members", crf::kMaxGenericMembers));
-    if ((p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC) && (p->num_bins < 1 || p->num_bins > 255))
-        return fail(c, CRF_ERR_ARGUMENT, fmt("num_bins %d outside [1,255]", p->num_bins));
-    // any k >= 1, like the reference (its k+1-nearest-neighbour query returns at most cs points; psi(k) itself is used)
-    if ((p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) && p->k < 1)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be at least 1", p->k));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling) {
-        e0 = take_event(c);
-        e1 = take_event(c);
-        (void)hipEventRecord(e0, s);
-    }
-    hipError_t e = hipErrorNotSupported;
-    if (p->measure == CRF_PEARSON) {
-        e = crf::launch_pearson_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, out, s);
-        c->last_kernel = "pearson_symmetric_kernel";
-    }
-    if (p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) {
-        e = crf::launch_mi_kraskov_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->k,
-                                             kraskov_c_term(p->k, 1), p->measure == CRF_KMI_CC, c->d_tables, out, s);
-        c->last_kernel = "kraskov_direct_kernel";
-    }
-    if (p->measure == CRF_SPEARMAN || p->measure == CRF_KENDALL || p->measure == CRF_MI_BINNED ||
-        p->measure == CRF_BINNED_MI_CC) {
-        const char* force_direct = getenv("CRF_SYMMETRIC_DIRECT");  // tuning / tests: the any-member-count kernel
-        if (!(force_direct && *force_direct == '1')) {
-            e = crf::launch_sorted_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->measure,
-                                             p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables,
-                                             out, s);
-            c->last_kernel = "sorted_symmetric_kernel";
-        }
-    }
-    if (e == hipErrorNotSupported && (p->measure == CRF_SPEARMAN || p->measure == CRF_KENDALL ||
-                                      p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC)) {
-        if (int r = ensure_workspace(c, crf::direct_symmetric_workspace_bytes(c->cs, c->num_voxels, p->measure))) return r;
-        e = crf::launch_direct_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->measure, p->num_bins,
-                                         p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables, c->d_workspace,
-                                         out, s);
-        c->last_kernel = "direct_symmetric_kernel";
-    }
-    if (e == hipErrorNotSupported) {
-        if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, c->num_voxels))) return r;
-        const crf::PairArgs a{p->measure, p->num_bins, p->k, 0, 1, p->min_ref, p->max_ref, p->min_query, p->max_query,
-                              kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
-        e = crf::launch_pair_requests(c->d_member_table, c->d_sec_table, c->cs, c->xs, c->ys, c->num_voxels, nullptr,
-                                      c->num_voxels, a, c->d_tables, c->d_workspace, out, s);
-        c->last_kernel = "pair_request_kernel";
-    }
-    if (e0 && e1) {
-        (void)hipEventRecord(e1, s);
-        c->ev_pending.emplace_back(e0, e1);
-    }
-    if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-    return CRF_OK;
-}
-
-static int ref_voxel(crf_context* c, int x, int y, int z, size_t* voxel) {
-    if (x < 0 || y < 0 || z < 0 || x >= c->xs || y >= c->ys || z >= c->zs)
-        return fail(c, CRF_ERR_ARGUMENT,
-                    fmt("reference point (%d,%d,%d) outside the local grid %dx%dx%d", x, y, z, c->xs, c->ys, c->zs));
-    *voxel = (size_t(z) * size_t(c->ys) + size_t(y)) * size_t(c->xs) + size_t(x);  // IDXS, DataSet.hpp:37
-    return CRF_OK;
-}
-
 int crf_gather_reference_device(crf_context* c, int x, int y, int z, void* device_out, void* stream) {
     if (int r = check_ready(c)) return r;
     if (!device_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
     size_t voxel;
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = stream_of(c, stream);
     CRF_HIP(c, crf::launch_gather_reference(c->d_member_table, c->cs, voxel, static_cast<float*>(device_out), s));
     return CRF_OK;
 }
@@ -671,7 +1044,7 @@ int crf_gather_reference_rows_device(crf_context* c, const int32_t* xyz, int num
             if (int e = ref_voxel(c, xyz[3 * r], xyz[3 * r + 1], xyz[3 * r + 2], &rows.voxel[r])) return e;
     }
     if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = stream_of(c, stream);
     CRF_HIP(c, crf::launch_gather_reference_rows(c->d_member_table, c->cs, rows, num_rows,
                                                  static_cast<float*>(device_rows), s));
     return CRF_OK;
@@ -685,422 +1058,7 @@ int crf_gather_reference(crf_context* c, int x, int y, int z, float* host_out) {
     return CRF_OK;
 }
 
-// ---- device result -> the caller's (pageable) host buffer -------------------------------------------------------------
-// The caller of calculateCpu owns a freshly allocated `new float[xs*ys*zs]` (VolumeData.cpp:1222-1226): pageable and never
-// touched.  Measured on MI355X hosts at 256^3 (67 MB, profiles/r03_host_boundary.md): one DMA into pinned memory 1.19 ms
-// (56.5 GB/s, the PCIe floor); a kernel storing straight into device-mapped pinned memory 1.22 ms; 8 host threads move
-// pinned -> resident pageable memory at 120 GB/s but only at 14 GB/s into never-touched pages (first-touch faults).
-//
-// So a host-output evaluation is a pipeline over a few voxel RANGES (ensure_host_ranges):
-//   GPU     the per-voxel kernel of each range stores its results straight into a pinned, device-mapped staging buffer
-//           (no device-side result buffer, no DMA engine: the stores cross PCIe while the kernel runs -- the kernel is
-//           simply throttled to the link rate, which is the floor anyway);
-//   host    a persistent pool of copier threads (crf_pool.h) moves each finished range from the staging buffer into
-//           the caller's buffer, and while it waits for a range it faults the destination pages of the ranges ahead in
-//           (MADV_POPULATE_WRITE batches the faults; transparent huge pages are requested for the buffer first).
-// Range sizes are staggered over two streams so that kernel ends alternate and the last copy is small (ensure_host_ranges).
-// CRF_HOST_PATH=dma keeps results in HBM and copies each range with the DMA engine instead (also used when a post-pass
-// has to read the result back: CRF_FLAG_ABSOLUTE_VALUE).
-constexpr int kMadvPopulateWrite = 23;  // MADV_POPULATE_WRITE (Linux 5.14), not in every libc header
-constexpr size_t kPage = 4096;
-
-static int env_int_or(const char* name, int fallback) {
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : fallback;
-}
-
-// faults [lo, hi) of the caller's buffer in (write access); mode 0: leave it to the copy, 1: touch, 2: populate
-static void fault_in(char* base, size_t lo, size_t hi, int mode) {
-    if (mode == 0 || lo >= hi) return;
-    const uintptr_t a = (reinterpret_cast<uintptr_t>(base) + lo) & ~(kPage - 1);
-    const uintptr_t e = (reinterpret_cast<uintptr_t>(base) + hi + kPage - 1) & ~(kPage - 1);
-    if (mode == 2 && madvise(reinterpret_cast<void*>(a), e - a, kMadvPopulateWrite) == 0) return;
-    // fallback / mode 1: one write per page.  The bytes written are inside the caller's buffer and are overwritten by
-    // the result afterwards.
-    for (size_t off = lo; off < hi; off += kPage) static_cast<volatile char*>(base)[off] = 0;
-    static_cast<volatile char*>(base)[hi - 1] = 0;
-}
-
-// thread w's share of byte range [r_lo, r_hi) among `workers` threads, split on page boundaries
-static void thread_share(size_t r_lo, size_t r_hi, int w, int workers, size_t* lo, size_t* hi) {
-    const size_t per = (((r_hi - r_lo) + size_t(workers) - 1) / size_t(workers) + kPage - 1) & ~(kPage - 1);
-    *lo = std::min(r_hi, r_lo + size_t(w) * per);
-    *hi = std::min(r_hi, *lo + per);
-}
-
-static int ensure_copy_pool(crf_context* c) {
-    if (c->copy_pool) return CRF_OK;
-    const unsigned hw = std::thread::hardware_concurrency();
-    int cap = int(std::min<unsigned>(16u, std::max(1u, hw / 2)));
-    if (c->copy_threads_cap > 0) cap = std::min(cap, c->copy_threads_cap);
-    const int forced = env_int_or("CRF_COPY_THREADS", 0);
-    if (forced >= 1) cap = std::min(forced, 64);
-    // copier threads idle-spin for a short while only: back-to-back evaluations hand over within ~0.1 ms
-    c->copy_pool = std::make_unique<crf::SpinPool>(cap, nullptr, 300e-6);
-    c->copy_threads = cap;
-    if (forced >= 1 || cap <= 2) return CRF_OK;
-    // one-off calibration: how many of the pool's threads move pinned -> pageable memory fastest on this host
-    const size_t bytes = std::min<size_t>(c->alloc_voxels * sizeof(float), size_t(16) << 20);
-    std::vector<char> dst(bytes, 1);
-    const char* src = reinterpret_cast<const char*>(c->h_staging);
-    double best = 1e30;
-    for (int t : {2, 4, 8, 12, 16}) {
-        if (t > cap) break;
-        double fastest = 1e30;
-        for (int rep = 0; rep < 3; rep++) {
-            const auto t0 = std::chrono::steady_clock::now();
-            c->copy_pool->run([&](int w) -> int {
-                if (w >= t) return 0;
-                size_t lo, hi;
-                thread_share(0, bytes, w, t, &lo, &hi);
-                if (lo < hi) memcpy(dst.data() + lo, src + lo, hi - lo);
-                return 0;
-            });
-            fastest = std::min(fastest, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-        }
-        if (fastest < best * 0.93) {  // more threads only for a real gain
-            best = fastest;
-            c->copy_threads = t;
-        }
-    }
-    return CRF_OK;
-}
-
-// Plain form for small results and the sibling reductions: kernel into HBM, one copy.
-static int copy_result_to_host(crf_context* c, const float* d_src, float* host_out, size_t count) {
-    CRF_HIP(c, hipMemcpyAsync(host_out, d_src, count * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    CRF_HIP(c, hipStreamSynchronize(c->stream));
-    return CRF_OK;
-}
-
-// phase: bit 0 = reference-side preparation, bit 1 = per-voxel kernel (crf_internal.h RefSource::phase);
-// slot < 0: the context's own preparation buffer
-static int compute_impl_one(crf_context* c, const crf_params* p, const void* device_reference_values, void* device_out,
-                            void* stream, unsigned phase, int slot, const crf::RefOverride* ov);
-
-// An ordinary grid: one call.  A grid whose members are 4 GiB or larger: the reference side once, from the whole grid
-// (the reference point indexes it with 64 bits), then the per-voxel kernel window by window.
-static int compute_impl(crf_context* c, const crf_params* p, const void* device_reference_values, void* device_out,
-                        void* stream, unsigned phase, int slot, const crf::RefOverride* ov = nullptr) {
-    if (!c || !c->windowed || !p || (p->flags & CRF_FLAG_SYMMETRIC))
-        return compute_impl_one(c, p, device_reference_values, device_out, stream, phase, slot, ov);
-    if (phase & 1u)
-        if (int r = compute_impl_one(c, p, device_reference_values, nullptr, stream, 1u, slot, ov)) return r;
-    if (!(phase & 2u)) return CRF_OK;
-    if (!device_out) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    return for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
-        return compute_impl_one(c, p, nullptr, o, stream, 2u, slot, nullptr);
-    });
-}
-
-static int compute_impl_one(crf_context* c, const crf_params* p, const void* device_reference_values, void* device_out,
-                            void* stream, unsigned phase, int slot, const crf::RefOverride* ov) {
-    if (int r = check_ready(c)) return r;
-    if (!p || (!device_out && (phase & 2u))) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (p->measure < CRF_PEARSON || p->measure > CRF_KMI_CC)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("unknown measure %d", p->measure));
-    for (int v : p->reserved)
-        if (v != 0) return fail(c, CRF_ERR_ARGUMENT, "crf_params.reserved must be zero");
-    if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    float* out = static_cast<float*>(device_out);
-    if (p->flags & CRF_FLAG_SYMMETRIC) {
-        if (phase != 3u) return fail(c, CRF_ERR_ARGUMENT, "the symmetric mode has no reference-side preparation");
-        return for_each_window(c, out, [&](float* o) { return compute_symmetric(c, p, o, s); });
-    }
-    float* prep = c->d_prep;
-    if (slot >= 0) {
-        if (!c->d_prep_slots)
-            CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_prep_slots), size_t(CRF_PREPARED_SLOTS) * crf::kPrepBytes));
-        prep = c->d_prep_slots + size_t(slot) * (crf::kPrepBytes / sizeof(float));
-    }
-
-    // 1. reference vector (CorrelationCalculator.cpp:802-818): a device array, a host array (copied stream-ordered),
-    //    or the reference point -- then the gather is fused into the estimator's preparation kernel.
-    crf::RefSource ref{static_cast<const float*>(device_reference_values), 0};
-    ref.phase = phase;
-    if (!(phase & 1u)) {
-        ref.values = nullptr;  // prepared earlier: no reference vector is read
-    } else if (!ref.values && ov) {
-        // crf_group, direct exchange: the preparation kernel reads the values out of another context's members
-        ref.table = ov->table;
-        ref.voxel = ov->voxel;
-    } else if (!ref.values && (p->flags & CRF_FLAG_REFERENCE_FROM_SECONDARY)) {
-        if (c->sec_members.empty())
-            return fail(c, CRF_ERR_STATE, "CRF_FLAG_REFERENCE_FROM_SECONDARY needs secondary members");
-        size_t voxel;
-        if (int r = ref_voxel(c, p->ref_x, p->ref_y, p->ref_z, &voxel)) return r;
-        CRF_HIP(c, crf::launch_gather_reference(c->d_sec_table, c->cs, voxel, c->d_ref, s));
-        ref.values = c->d_ref;
-    }
-    if ((phase & 1u) && !ref.values && !ref.table) {
-        if (p->reference_values) {
-            CRF_HIP(c, hipMemcpyAsync(c->d_ref, p->reference_values, sizeof(float) * size_t(c->cs),
-                                      hipMemcpyHostToDevice, s));
-            ref.values = c->d_ref;
-        } else {
-            if (int r = ref_voxel(c, p->ref_x, p->ref_y, p->ref_z, &ref.voxel)) return r;
-        }
-    }
-
-    // 2. estimator
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling && (phase & 2u)) {
-        e0 = take_event(c);
-        e1 = take_event(c);
-    }
-    const int vpt = std::min(c->max_vpt, alignment_vpt(out));
-    crf::LaunchInfo info;
-    hipError_t e = hipSuccess;
-    if (p->measure != CRF_PEARSON && c->cs > crf::kMaxSortMembers) {
-        // any-member-count path (kernels_generic.hip)
-        if (c->cs > crf::kMaxGenericMembers)
-            return fail(c, CRF_ERR_UNSUPPORTED, fmt("measure %d supports at most %d members (got %d)", p->measure,
-                                                    crf::kMaxGenericMembers, c->cs));
-        if ((p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC) && (p->num_bins < 1 || p->num_bins > 255))
-            return fail(c, CRF_ERR_ARGUMENT, fmt("num_bins %d outside [1,255]", p->num_bins));
-        if ((p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) && p->k < 1)
-            return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be at least 1", p->k));
-        if (p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC) {  // O(cs) histogram kernel
-            crf::BinnedArgs ba{p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query,
-                               p->measure == CRF_BINNED_MI_CC};
-            e = crf::launch_mi_binned_hist(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s, e0,
-                                           e1, &info);
-            if (e != hipErrorNotSupported) {
-                c->last_kernel = info.kernel_name ? info.kernel_name : "";
-                if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
-                if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-                return CRF_OK;
-            }
-            e = hipSuccess;  // too many bins for the LDS rows: the O(cs^2) kernel below
-        }
-        if (p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) {  // tile-free single-sweep top-K kernel
-            const int est = p->kraskov_estimator_index == 2 ? 2 : 1;
-            crf::KraskovArgs ka{p->k, est, p->measure == CRF_KMI_CC, kraskov_c_term(p->k, est)};
-            e = crf::launch_mi_kraskov_direct(c->d_member_table, c->cs, c->num_voxels, ref, ka, c->d_tables, prep, out, s,
-                                              e0, e1, &info);
-            if (e != hipErrorNotSupported) {
-                c->last_kernel = info.kernel_name ? info.kernel_name : "";
-                if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
-                if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-                return CRF_OK;
-            }
-            e = hipSuccess;  // k > 128 or tables beyond LDS: the repeated-minimum kernel below
-        }
-        if (int r = ensure_workspace(c, crf::generic_workspace_bytes(c->cs, c->num_voxels))) return r;
-        crf::GenericArgs ga{p->measure, p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, p->k,
-                            p->kraskov_estimator_index == 2 ? 2 : 1,
-                            kraskov_c_term(p->k > 0 ? p->k : 1, p->kraskov_estimator_index == 2 ? 2 : 1)};
-        const bool rank_measure = p->measure == CRF_SPEARMAN || p->measure == CRF_KENDALL;
-        if (rank_measure && c->cs <= 256 && !c->d_todo)  // the sort-based kernels' list of deferred voxels
-            CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_todo), (c->alloc_voxels + 1) * sizeof(uint32_t)));
-        e = crf::launch_generic(c->d_member_table, c->cs, c->num_voxels, ref, ga, c->d_tables, prep, c->d_workspace,
-                                out, s, e0, e1, &info, rank_measure ? c->d_todo : nullptr);
-        c->last_kernel = info.kernel_name ? info.kernel_name : "";
-        if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
-        if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-        return CRF_OK;
-    }
-    switch (p->measure) {
-        case CRF_PEARSON: {
-            crf::PackedMembers packed;
-            if (phase & 2u)
-                if (int r = ensure_packed(c, s, &packed)) return r;
-            e = crf::launch_pearson(c->d_member_table, c->cs, c->num_voxels, vpt, ref, prep, out, s, e0, e1,
-                                    &info, packed);
-            if (phase & 2u) c->last_layout = packed.header ? CRF_MEMBER_LAYOUT_PACKED : CRF_MEMBER_LAYOUT_RAW;
-            break;
-        }
-        case CRF_SPEARMAN:
-            if (c->cs > crf::kMaxSortMembers)
-                return fail(c, CRF_ERR_UNSUPPORTED, fmt("Spearman supports at most %d members", crf::kMaxSortMembers));
-            if (c->cs > 16 && !c->d_todo)
-                CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_todo), (c->alloc_voxels + 1) * sizeof(uint32_t)));
-            e = crf::launch_spearman(c->d_member_table, c->cs, c->num_voxels, ref, prep, c->d_todo, out, s, e0, e1,
-                                     &info);
-            break;
-        case CRF_KENDALL:
-            if (c->cs > crf::kMaxSortMembers)
-                return fail(c, CRF_ERR_UNSUPPORTED, fmt("Kendall supports at most %d members", crf::kMaxSortMembers));
-            if (c->cs > 16 && !c->d_todo)
-                CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_todo), (c->alloc_voxels + 1) * sizeof(uint32_t)));
-            e = crf::launch_kendall(c->d_member_table, c->cs, c->num_voxels, ref, prep, c->d_todo, out, s, e0, e1,
-                                    &info);
-            break;
-        case CRF_MI_BINNED:
-        case CRF_BINNED_MI_CC: {
-            if (p->num_bins < 1 || p->num_bins > 255)
-                return fail(c, CRF_ERR_ARGUMENT, fmt("num_bins %d outside [1,255]", p->num_bins));
-            if (c->cs > crf::kMaxSortMembers)
-                return fail(c, CRF_ERR_UNSUPPORTED, fmt("binned MI supports at most %d members", crf::kMaxSortMembers));
-            crf::BinnedArgs a{p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query,
-                              p->measure == CRF_BINNED_MI_CC};
-            if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1') {  // tuning: histogram kernel for any cs
-                e = crf::launch_mi_binned_hist(c->d_member_table, c->cs, c->num_voxels, ref, a, c->d_tables, prep, out, s,
-                                               e0, e1, &info);
-                if (e != hipErrorNotSupported) break;
-            }
-            e = crf::launch_mi_binned(c->d_member_table, c->cs, c->num_voxels, ref, a, c->d_tables, prep, out, s,
-                                      e0, e1, &info);
-            break;
-        }
-        case CRF_MI_KRASKOV:
-        case CRF_KMI_CC: {
-            if (p->k < 1) return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be at least 1", p->k));
-            if (c->cs > crf::kMaxSortMembers)
-                return fail(c, CRF_ERR_UNSUPPORTED, fmt("Kraskov MI supports at most %d members", crf::kMaxSortMembers));
-            const int est = p->kraskov_estimator_index == 2 ? 2 : 1;  // clamp as CorrelationCalculator.cpp:765
-            crf::KraskovArgs a{p->k, est, p->measure == CRF_KMI_CC, kraskov_c_term(p->k, est)};
-            e = crf::launch_mi_kraskov(c->d_member_table, c->cs, c->num_voxels, ref, a, c->d_tables, prep, out, s,
-                                       e0, e1, &info);
-            break;
-        }
-    }
-    c->last_kernel = info.kernel_name ? info.kernel_name : "";
-    if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
-    if (e == hipErrorNotSupported)
-        return fail(c, CRF_ERR_UNSUPPORTED, fmt("measure %d is not implemented by this build", p->measure));
-    if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-    return CRF_OK;
-}
-
-int crf_compute_device(crf_context* c, const crf_params* p, const void* device_reference_values, void* device_out,
-                       void* stream) {
-    int rc;
-    if (p && p->prepared_slot != 0) {
-        if (p->prepared_slot < 0 || p->prepared_slot > CRF_PREPARED_SLOTS)
-            return fail(c, CRF_ERR_ARGUMENT, fmt("prepared_slot %d outside [0,%d]", p->prepared_slot, CRF_PREPARED_SLOTS));
-        if (c && !c->d_prep_slots) return fail(c, CRF_ERR_STATE, "prepared_slot given but crf_prepare_device was never called");
-        rc = compute_impl(c, p, nullptr, device_out, stream, 2u, p->prepared_slot - 1);
-    } else {
-        rc = compute_impl(c, p, device_reference_values, device_out, stream, 3u, -1);
-    }
-    if (rc == CRF_OK && (p->flags & CRF_FLAG_ABSOLUTE_VALUE)) {  // opt-in: what the reference's accelerator paths do
-        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-        CRF_HIP(c, crf::launch_abs(static_cast<float*>(device_out), c->num_voxels, s));
-    }
-    return rc;
-}
-
-int crf_prepare_rows_device(crf_context* c, const crf_params* p, const void* device_rows, int first_slot, int count,
-                            void* stream) {
-    if (!c || !p || !device_rows) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (count < 0 || first_slot < 0 || first_slot + count > CRF_PREPARED_SLOTS)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("slots [%d, %d) outside [0, %d)", first_slot, first_slot + count, CRF_PREPARED_SLOTS));
-    crf_params local = *p;
-    local.reference_values = nullptr;
-    local.prepared_slot = 0;
-    const float* rows = static_cast<const float*>(device_rows);
-    for (int i = 0; i < count; i++)
-        if (int r = crf_prepare_device(c, &local, rows + size_t(i) * size_t(c->cs), first_slot + i, stream)) return r;
-    return CRF_OK;
-}
-
-int crf_compute_prepared_device(crf_context* c, const crf_params* p, int first_slot, int count, void* const* device_outs,
-                                void* stream) {
-    if (!c || !p || !device_outs) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (count < 0 || first_slot < 0 || first_slot + count > CRF_PREPARED_SLOTS)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("slots [%d, %d) outside [0, %d)", first_slot, first_slot + count, CRF_PREPARED_SLOTS));
-    crf_params local = *p;
-    for (int i = 0; i < count; i++) {
-        local.prepared_slot = first_slot + i + 1;
-        if (int r = crf_compute_device(c, &local, nullptr, device_outs[i], stream)) return r;
-    }
-    return CRF_OK;
-}
-
-int crf_prepare_device(crf_context* c, const crf_params* p, const void* device_reference_values, int slot, void* stream) {
-    if (slot < 0 || slot >= CRF_PREPARED_SLOTS)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("slot %d outside [0,%d)", slot, CRF_PREPARED_SLOTS));
-    return compute_impl(c, p, device_reference_values, nullptr, stream, 1u, slot);
-}
-
-int crf_compute(crf_context* c, const crf_params* p, float* host_out) {
-    return crf::compute_to_host(c, p, nullptr, host_out, nullptr);
-}
-
 }  // extern "C"
-
-namespace {
-// The voxel ranges of a host-output evaluation: one member-pointer table per range (pointers advanced by the range's
-// first voxel), so that every per-voxel kernel can be launched on a range without knowing about ranges.  Range lengths
-// are multiples of 1024 voxels (4 KiB: every range stays as aligned as the members themselves) and shrink towards the
-// end: the copy of the last range into the caller's buffer is the only host work no kernel hides.
-int ensure_host_ranges(crf_context* c) {
-    if (c->host_chunks > 0) return CRF_OK;
-    const size_t n = c->alloc_voxels;
-    std::vector<size_t> first{0};
-    const int forced = env_int_or("CRF_HOST_CHUNKS", 0);
-    if (forced >= 1) {  // experiments: equal ranges
-        size_t per = (n + size_t(forced) - 1) / size_t(forced);
-        per = (per + 1023) & ~size_t(1023);
-        for (size_t at = per; at < n && int(first.size()) < kMaxHostChunks; at += per) first.push_back(at);
-    } else {
-        // Shares of 64, consecutive ranges alternating between two streams: 3 6 6 6 6 6 6 6 6 5 4 2 2.  The two streams'
-        // kernels run concurrently and share the link; with the FIRST range half the size of the others the kernel ends
-        // alternate (B0 A0 B1 A1 ...), so results land every ~1/11 of the run from early on, the copier threads always
-        // have a landed range to move, and the last ranges are small: only their copy is not hidden behind a kernel.
-        // Same-process A/B at 256^3 (tools/measure_host_path.py ab, profiles/r03_host_boundary_variants.txt), resident /
-        // fresh destination: 13 ranges 1.326 / 1.391 ms; 11 ranges (4 8x6 6 3 2 1) 1.336 / 1.452; 8 staggered ranges
-        // 1.369 / 1.467; 8 shrinking ranges 16 14 11 8 6 4 3 2 (pairs end together) 1.378 / 1.527; 8 equal 1.450 / 1.644.
-        std::vector<int> kShares = {3, 6, 6, 6, 6, 6, 6, 6, 6, 5, 4, 2, 2};
-        if (const char* e = getenv("CRF_HOST_SHARES")) {  // experiments: comma-separated shares of 64
-            std::vector<int> v;
-            int sum = 0;
-            for (const char* q = e; *q;) {
-                v.push_back(atoi(q));
-                sum += v.back();
-                while (*q && *q != ',') q++;
-                if (*q == ',') q++;
-            }
-            if (sum == 64 && v.size() >= 1 && v.size() <= size_t(kMaxHostChunks)) kShares = v;
-        }
-        size_t acc = 0;
-        for (int j = 0; j + 1 < int(kShares.size()); j++) {
-            acc += size_t(kShares[size_t(j)]);
-            const size_t at = (n / 64 * acc + 1023) & ~size_t(1023);
-            if (at > first.back() && at < n) first.push_back(at);
-        }
-    }
-    const int ranges = int(first.size());
-    first.push_back(n);
-    std::vector<const float*> table(size_t(ranges) * size_t(c->cs));
-    for (int j = 0; j < ranges; j++)
-        for (int m = 0; m < c->cs; m++) table[size_t(j) * size_t(c->cs) + size_t(m)] = c->members[size_t(m)] + first[size_t(j)];
-    if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
-    c->d_chunk_tables = nullptr;
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_chunk_tables), table.size() * sizeof(float*)));
-    CRF_HIP(c, hipMemcpy(c->d_chunk_tables, table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
-    if (!c->copy_stream) CRF_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int j = 0; j < ranges; j++)
-        if (!c->chunk_done[j]) CRF_HIP(c, hipEventCreateWithFlags(&c->chunk_done[j], hipEventDisableTiming));
-    for (int j = 0; j < ranges; j++)
-        if (!c->chunk_copied[j]) CRF_HIP(c, hipEventCreateWithFlags(&c->chunk_copied[j], hipEventDisableTiming));
-    if (!c->prep_done) CRF_HIP(c, hipEventCreateWithFlags(&c->prep_done, hipEventDisableTiming));
-    for (int j = 0; j <= ranges; j++) c->chunk_first[j] = first[size_t(j)];
-    c->host_chunks = ranges;
-    return CRF_OK;
-}
-
-// narrows the context to one voxel range for the duration of a launch; restores it on every exit path
-struct RangeScope {
-    crf_context* c;
-    const float** table;
-    size_t voxels;
-    int vpt;
-    explicit RangeScope(crf_context* ctx) : c(ctx), table(ctx->d_member_table), voxels(ctx->num_voxels), vpt(ctx->max_vpt) {}
-    void select(int j) {
-        c->d_member_table = c->d_chunk_tables + size_t(j) * size_t(c->cs);
-        c->num_voxels = c->chunk_first[j + 1] - c->chunk_first[j];
-    }
-    ~RangeScope() {
-        c->d_member_table = table;
-        c->num_voxels = voxels;
-        c->max_vpt = vpt;
-    }
-};
-
-}  // namespace
 
 namespace crf {
 
@@ -1133,18 +1091,13 @@ int compute_device_ex(crf_context* c, const crf_params* p, const void* device_re
                       void* stream, const RefOverride* ov) {
     if (!ov) return crf_compute_device(c, p, device_reference_values, device_out, stream);
     if (!p || p->prepared_slot != 0) return fail(c, CRF_ERR_ARGUMENT, "a direct reference read cannot use a prepared slot");
-    const int rc = compute_impl(c, p, device_reference_values, device_out, stream, 3u, -1, ov);
-    if (rc == CRF_OK && (p->flags & CRF_FLAG_ABSOLUTE_VALUE)) {
-        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-        CRF_HIP(c, crf::launch_abs(static_cast<float*>(device_out), c->num_voxels, s));
-    }
-    return rc;
+    if (int r = compute_impl(c, p, device_reference_values, device_out, stream, 3u, -1, ov)) return r;
+    return apply_abs(c, p, device_out, stream);
 }
 
 int prepare_device_ex(crf_context* c, const crf_params* p, const void* device_reference_values, int slot, void* stream,
                       const RefOverride* ov) {
-    if (slot < 0 || slot >= CRF_PREPARED_SLOTS)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("slot %d outside [0,%d)", slot, CRF_PREPARED_SLOTS));
+    if (int r = check_slots(c, slot, 1, true)) return r;
     return compute_impl(c, p, device_reference_values, nullptr, stream, 1u, slot, ov);
 }
 
@@ -1160,7 +1113,7 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
     const bool ranged = !(p->flags & CRF_FLAG_SYMMETRIC) && p->prepared_slot == 0 && bytes >= (size_t(8) << 20) &&
                         !c->windowed && env_int_or("CRF_PLAIN_D2H", 0) != 1;
     if (!ranged) {
-        if (!c->d_out) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), bytes));
+        if (int r = ensure_out(c)) return r;
         if (int r = compute_device_ex(c, p, device_reference_values, c->d_out, nullptr, ov)) return r;
         return copy_result_to_host(c, c->d_out, host_out, c->alloc_voxels);
     }
@@ -1176,7 +1129,8 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
     if (int r = ensure_copy_pool(c)) return r;
     const char* path_env = getenv("CRF_HOST_PATH");
     const bool dma = (path_env && strcmp(path_env, "dma") == 0) || (p->flags & CRF_FLAG_ABSOLUTE_VALUE);
-    if (dma && !c->d_out) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), bytes));
+    if (dma)
+        if (int r = ensure_out(c)) return r;
     {
         hipStream_t unused;
         if (int r = second_stream(c, &unused)) return r;
@@ -1240,9 +1194,9 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
     //    last waves of the previous one drain); results go straight to the mapped staging buffer, or to HBM + DMA
     float* out_base = dma ? c->d_out : c->d_staging;
     {
-        RangeScope scope(c);
+        NarrowScope scope(c);
         for (int j = 0; j < ranges; j++) {
-            scope.select(j);
+            scope.select_range(j);
             hipStream_t s = (two_streams && !(j & 1)) ? c->stream2 : c->stream;  // range 0 on the second stream
             float* out = out_base + c->chunk_first[j];
             if (int r = compute_impl(c, p, nullptr, out, s, 2u, -1)) return abort_copy(r);
@@ -1277,24 +1231,63 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
 
 extern "C" {
 
+// ---- field evaluation -------------------------------------------------------------------------------------------------
+int crf_compute_device(crf_context* c, const crf_params* p, const void* device_reference_values, void* device_out,
+                       void* stream) {
+    if (p && p->prepared_slot != 0) {
+        if (p->prepared_slot < 0 || p->prepared_slot > CRF_PREPARED_SLOTS)
+            return fail(c, CRF_ERR_ARGUMENT, fmt("prepared_slot %d outside [0,%d]", p->prepared_slot, CRF_PREPARED_SLOTS));
+        if (c && !c->d_prep_slots) return fail(c, CRF_ERR_STATE, "prepared_slot given but crf_prepare_device was never called");
+        if (int r = compute_impl(c, p, nullptr, device_out, stream, 2u, p->prepared_slot - 1)) return r;
+    } else {
+        if (int r = compute_impl(c, p, device_reference_values, device_out, stream, 3u, -1)) return r;
+    }
+    return apply_abs(c, p, device_out, stream);
+}
+
+int crf_prepare_device(crf_context* c, const crf_params* p, const void* device_reference_values, int slot, void* stream) {
+    return crf::prepare_device_ex(c, p, device_reference_values, slot, stream, nullptr);
+}
+
+int crf_prepare_rows_device(crf_context* c, const crf_params* p, const void* device_rows, int first_slot, int count,
+                            void* stream) {
+    if (!c || !p || !device_rows) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (int r = check_slots(c, first_slot, count)) return r;
+    crf_params local = *p;
+    local.reference_values = nullptr;
+    local.prepared_slot = 0;
+    const float* rows = static_cast<const float*>(device_rows);
+    for (int i = 0; i < count; i++)
+        if (int r = crf_prepare_device(c, &local, rows + size_t(i) * size_t(c->cs), first_slot + i, stream)) return r;
+    return CRF_OK;
+}
+
+int crf_compute_prepared_device(crf_context* c, const crf_params* p, int first_slot, int count, void* const* device_outs,
+                                void* stream) {
+    if (!c || !p || !device_outs) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (int r = check_slots(c, first_slot, count)) return r;
+    crf_params local = *p;
+    for (int i = 0; i < count; i++) {
+        local.prepared_slot = first_slot + i + 1;
+        if (int r = crf_compute_device(c, &local, nullptr, device_outs[i], stream)) return r;
+    }
+    return CRF_OK;
+}
+
+int crf_compute(crf_context* c, const crf_params* p, float* host_out) {
+    return crf::compute_to_host(c, p, nullptr, host_out, nullptr);
+}
+
+// ---- pair requests ----------------------------------------------------------------------------------------------------
 int crf_compute_requests_device(crf_context* c, const crf_params* p, const void* device_requests, size_t num_requests,
                                 void* device_out, void* stream) {
     if (int r = check_ready(c)) return r;
-    if (!p || (num_requests && (!device_requests || !device_out))) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (p->measure < CRF_PEARSON || p->measure > CRF_KMI_CC)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("unknown measure %d", p->measure));
-    for (int v : p->reserved)
-        if (v != 0) return fail(c, CRF_ERR_ARGUMENT, "crf_params.reserved must be zero");
-    if (c->cs > crf::kMaxGenericMembers)
-        return fail(c, CRF_ERR_UNSUPPORTED, fmt("pair requests support at most %d members", crf::kMaxGenericMembers));
+    if (int r = check_params(c, p, crf::kMaxGenericMembers, "pair requests support")) return r;
+    if (num_requests && (!device_requests || !device_out)) return fail(c, CRF_ERR_ARGUMENT, "null argument");
     if (c->windowed)
         return fail(c, CRF_ERR_UNSUPPORTED, "pair requests address voxels with 32-bit byte offsets: member volumes of 4 GiB or more are not supported in request mode");
-    if ((p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC) && (p->num_bins < 1 || p->num_bins > 255))
-        return fail(c, CRF_ERR_ARGUMENT, fmt("num_bins %d outside [1,255]", p->num_bins));
-    if ((p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) && p->k < 1)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be at least 1", p->k));
     if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = stream_of(c, stream);
     if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, num_requests))) return r;
     // two-field request mode: the j side reads the secondary members (CRF_FLAG_QUERY_FROM_SECONDARY)
     const float* const* members_j = c->d_member_table;
@@ -1330,8 +1323,7 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
                                       c->d_workspace, static_cast<float*>(device_out), s);
         c->last_kernel = "pair_request_kernel";
     }
-    if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-    return CRF_OK;
+    return launch_status(c, e);
 }
 
 int crf_compute_requests(crf_context* c, const crf_params* p, const crf_request* host_requests, size_t num_requests,
@@ -1364,37 +1356,19 @@ int crf_compute_requests(crf_context* c, const crf_params* p, const crf_request*
     return CRF_OK;
 }
 
+// ---- ensemble statistics ----------------------------------------------------------------------------------------------
 int crf_compute_ensemble_stat_device(crf_context* c, int stat, void* device_out, void* stream) {
     if (int r = check_ready(c)) return r;
     if (!device_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
     if (stat != CRF_ENSEMBLE_MEAN && stat != CRF_ENSEMBLE_SPREAD)
         return fail(c, CRF_ERR_ARGUMENT, fmt("unknown ensemble statistic %d", stat));
-    if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling) {
-        e0 = take_event(c);
-        e1 = take_event(c);
-    }
-    crf::LaunchInfo info;
-    hipError_t e = hipSuccess;
-    (void)for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
-        if (e == hipSuccess) e = crf::launch_ensemble_stat(stat, c->d_member_table, c->cs, c->num_voxels, o, s, e0, e1, &info);
-        return CRF_OK;
+    return run_windowed(c, device_out, stream, [&](float* o, hipStream_t s, TimedLaunch& t) {
+        return crf::launch_ensemble_stat(stat, c->d_member_table, c->cs, c->num_voxels, o, s, t.e0, t.e1, &t.info);
     });
-    c->last_kernel = info.kernel_name ? info.kernel_name : "";
-    if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
-    if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-    return CRF_OK;
 }
 
 int crf_compute_ensemble_stat(crf_context* c, int stat, float* host_out) {
-    if (int r = check_ready(c)) return r;
-    if (!host_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
-    if (int r = bind_device(c)) return r;
-    if (!c->d_out) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), c->num_voxels * sizeof(float)));
-    if (int r = crf_compute_ensemble_stat_device(c, stat, c->d_out, nullptr)) return r;
-    return copy_result_to_host(c, c->d_out, host_out, c->num_voxels);
+    return to_host(c, host_out, [&](void* d) { return crf_compute_ensemble_stat_device(c, stat, d, nullptr); });
 }
 
 int crf_compute_set_predicate_device(crf_context* c, int op, float comparison_value, int count_lower, int count_upper,
@@ -1403,36 +1377,17 @@ int crf_compute_set_predicate_device(crf_context* c, int op, float comparison_va
     if (!device_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
     if (op < CRF_CMP_GREATER || op > CRF_CMP_NOT_EQUAL)
         return fail(c, CRF_ERR_ARGUMENT, fmt("unknown comparison operator %d", op));
-    if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling) {
-        e0 = take_event(c);
-        e1 = take_event(c);
-    }
-    crf::LaunchInfo info;
-    hipError_t e = hipSuccess;
-    (void)for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
-        if (e == hipSuccess)
-            e = crf::launch_set_predicate(c->d_member_table, c->cs, c->num_voxels, op, comparison_value, count_lower, count_upper,
-                                          o, s, e0, e1, &info);
-        return CRF_OK;
+    return run_windowed(c, device_out, stream, [&](float* o, hipStream_t s, TimedLaunch& t) {
+        return crf::launch_set_predicate(c->d_member_table, c->cs, c->num_voxels, op, comparison_value, count_lower,
+                                         count_upper, o, s, t.e0, t.e1, &t.info);
     });
-    c->last_kernel = info.kernel_name ? info.kernel_name : "";
-    if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
-    if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-    return CRF_OK;
 }
 
 int crf_compute_set_predicate(crf_context* c, int op, float comparison_value, int count_lower, int count_upper,
                               float* host_out) {
-    if (int r = check_ready(c)) return r;
-    if (!host_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
-    if (int r = bind_device(c)) return r;
-    if (!c->d_out) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), c->num_voxels * sizeof(float)));
-    if (int r = crf_compute_set_predicate_device(c, op, comparison_value, count_lower, count_upper, c->d_out, nullptr))
-        return r;
-    return copy_result_to_host(c, c->d_out, host_out, c->num_voxels);
+    return to_host(c, host_out, [&](void* d) {
+        return crf_compute_set_predicate_device(c, op, comparison_value, count_lower, count_upper, d, nullptr);
+    });
 }
 
 int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, void* device_out, void* stream) {
@@ -1447,39 +1402,21 @@ int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, v
     if (estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 && (k < 1 || k >= c->cs))
         return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be in [1, cs-1=%d]", k, c->cs - 1));
     if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
     if (int r = ensure_workspace(c, crf::dkl_workspace_bytes(c->cs, estimator, num_bins, std::min(c->num_voxels, kWindowVoxels)))) return r;
     // psi(n) = -gamma + H_{n-1} (boost::math::digamma at positive integers, DKL.cpp:156)
     const double knn_const =
         estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 ? psi_int(c->cs) - psi_int(k) + std::log(2.0) : 0.0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->profiling) {
-        e0 = take_event(c);
-        e1 = take_event(c);
-    }
-    crf::LaunchInfo info;
-    hipError_t e = hipSuccess;
-    (void)for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
-        if (e == hipSuccess)
-            e = crf::launch_dkl(c->d_member_table, c->cs, c->num_voxels, estimator, num_bins, k, knn_const, c->d_workspace, o, s,
-                                e0, e1, &info);
-        return CRF_OK;
+    return run_windowed(c, device_out, stream, [&](float* o, hipStream_t s, TimedLaunch& t) {
+        return crf::launch_dkl(c->d_member_table, c->cs, c->num_voxels, estimator, num_bins, k, knn_const, c->d_workspace, o,
+                               s, t.e0, t.e1, &t.info);
     });
-    c->last_kernel = info.kernel_name ? info.kernel_name : "";
-    if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
-    if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-    return CRF_OK;
 }
 
 int crf_compute_dkl(crf_context* c, int estimator, int num_bins, int k, float* host_out) {
-    if (int r = check_ready(c)) return r;
-    if (!host_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
-    if (int r = bind_device(c)) return r;
-    if (!c->d_out) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), c->num_voxels * sizeof(float)));
-    if (int r = crf_compute_dkl_device(c, estimator, num_bins, k, c->d_out, nullptr)) return r;
-    return copy_result_to_host(c, c->d_out, host_out, c->num_voxels);
+    return to_host(c, host_out, [&](void* d) { return crf_compute_dkl_device(c, estimator, num_bins, k, d, nullptr); });
 }
 
+// ---- helpers, instrumentation, synthetic data -------------------------------------------------------------------------
 double crf_max_mutual_information_kraskov(int k, int cs) {
     if (k < 1 || cs < 1) return std::numeric_limits<double>::quiet_NaN();
     return psi_int(cs) - psi_int(k);
@@ -1496,11 +1433,10 @@ int crf_tile_field_device(crf_context* c, const void* device_linear, void* devic
     if (c->windowed) return fail(c, CRF_ERR_UNSUPPORTED, "re-tiling a field of 4 GiB or more is not supported");
     if (!device_linear || !device_tiled) return fail(c, CRF_ERR_ARGUMENT, "null argument");
     if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = stream_of(c, stream);
     hipError_t e = crf::launch_tile_field(static_cast<const float*>(device_linear), static_cast<float*>(device_tiled),
                                           c->xs, c->ys, c->zs, s);
-    if (e != hipSuccess) return fail(c, CRF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
-    return CRF_OK;
+    return launch_status(c, e);
 }
 
 int crf_set_profiling(crf_context* c, int enabled) {
@@ -1563,7 +1499,7 @@ int crf_synth_box_member(crf_context* c, void* device_out, int xs, int ys, int z
     if (xs <= 0 || ys <= 0 || zs_local <= 0 || zs_global <= 0 || z_begin < 0 || member < 0 || member >= cs)
         return fail(c, CRF_ERR_ARGUMENT, "invalid synthetic volume description");
     if (int r = bind_device(c)) return r;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t s = stream_of(c, stream);
     CRF_HIP(c, crf::launch_synth_box_member(static_cast<float*>(device_out), xs, ys, zs_local, z_begin, zs_global,
                                             member, cs, seed, s));
     return CRF_OK;

@@ -173,3 +173,170 @@ def test_absolute_value_is_opt_in(engine):
     assert (plain < 0).any()
     np.testing.assert_array_equal(absd, np.abs(plain))      # NaN stays NaN
     assert np.isnan(absd.reshape(6, 10, 12)[1, 1, 1])
+
+
+def _valid_params(measure=0, flags=0):
+    p = CrfParams()
+    p.measure, p.flags = measure, flags
+    p.ref_x, p.ref_y, p.ref_z = 1, 1, 1
+    p.k, p.kraskov_estimator_index, p.num_bins = 2, 1, 20
+    p.min_ref, p.max_ref, p.min_query, p.max_query = -4.0, 4.0, -4.0, 4.0
+    return p
+
+
+def _set(**fields):
+    def mutate(p):
+        for name, value in fields.items():
+            if name == "reserved":
+                p.reserved[value] = 1
+            else:
+                setattr(p, name, value)
+    return mutate
+
+
+def _mutated(p, mutate):
+    q = CrfParams.from_buffer_copy(p)
+    mutate(q)
+    return q
+
+
+# one fault in an otherwise valid crf_params: (what, mutation, status code, message substring); every evaluation mode
+# reports these the same way
+BAD_PARAMS = [
+    ("measure -1", _set(measure=-1), 1, "unknown measure -1"),
+    ("measure 99", _set(measure=99), 1, "unknown measure 99"),
+    ("reserved[0]", _set(reserved=0), 1, "reserved must be zero"),
+    ("reserved[1]", _set(reserved=1), 1, "reserved must be zero"),
+] + [(f"measure {m} num_bins {b}", _set(measure=m, num_bins=b), 1, f"num_bins {b} outside [1,255]")
+     for m in (int(Measure.MUTUAL_INFORMATION_BINNED), int(Measure.BINNED_MI_CORRELATION_COEFFICIENT)) for b in (0, 256)
+] + [(f"measure {m} k 0", _set(measure=m, k=0), 1, "k=0 must be at least 1")
+     for m in (int(Measure.MUTUAL_INFORMATION_KRASKOV), int(Measure.KMI_CORRELATION_COEFFICIENT))]
+
+
+@pytest.mark.parametrize("cs", [8, 160])          # the per-measure kernels / the any-member-count kernels
+def test_single_faults_keep_their_status_and_message(cs):
+    """Every call with exactly one thing wrong: the status code and the text of crf_last_error, for the field, symmetric
+    and request modes and for the slot-taking and statistics calls; the context stays usable after each."""
+    xs, ys, zs = 8, 8, 4
+    n = xs * ys * zs
+    ens = synth.box_ensemble(xs, ys, zs, cs, seed=cs)
+    host = np.empty(n, np.float32)
+    host_p = host.ctypes.data_as(C.POINTER(C.c_float))
+    dev = torch.empty(n, dtype=torch.float32, device="cuda")
+    dev_p = C.c_void_p(dev.data_ptr())
+    rows = torch.zeros((2, cs), dtype=torch.float32, device="cuda")
+    rows_p = C.c_void_p(rows.data_ptr())
+    outs_p = (C.c_void_p * 2)(dev.data_ptr(), dev.data_ptr())
+    req = np.zeros((1, 8), np.uint32)
+    req[0, 4:8] = (1, 1, 1, (1 * ys + 1) * xs + 1)
+    req_p = C.c_void_p(req.ctypes.data)
+    one = np.empty(1, np.float32)
+    one_p = one.ctypes.data_as(C.POINTER(C.c_float))
+    null_f, null_v = C.POINTER(C.c_float)(), C.c_void_p(0)
+    sym, ref_sec, query_sec = 2, 4, 8            # CRF_FLAG_SYMMETRIC, _REFERENCE_FROM_SECONDARY, _QUERY_FROM_SECONDARY
+    slots = ca.CorrField.PREPARED_SLOTS
+
+    plain, two = ca.CorrField(0), ca.CorrField(0)   # without / with secondary members
+    try:
+        for eng in (plain, two):
+            eng.set_grid(xs, ys, zs, cs)
+            eng.upload_members(ens)
+        two.upload_secondary_members(ens[::-1])
+        lib = plain._lib
+
+        def field(eng, p):
+            return lib.crf_compute(eng._ctx, C.byref(p), host_p)
+
+        def field_device(eng, p):
+            return lib.crf_compute_device(eng._ctx, C.byref(p), null_v, dev_p, null_v)
+
+        def requests(eng, p):
+            return lib.crf_compute_requests(eng._ctx, C.byref(p), req_p, 1, one_p)
+
+        def prepare(eng, p, slot):
+            return lib.crf_prepare_device(eng._ctx, C.byref(p), null_v, slot, null_v)
+
+        def prepare_rows(eng, p, first, count):
+            return lib.crf_prepare_rows_device(eng._ctx, C.byref(p), rows_p, first, count, null_v)
+
+        def compute_prepared(eng, p, first, count):
+            return lib.crf_compute_prepared_device(eng._ctx, C.byref(p), first, count, outs_p, null_v)
+
+        ok = _valid_params()
+        # (what, context, call, status code, message substring)
+        table = [("prepared_slot 1 before any crf_prepare_device", plain,
+                  lambda e: field_device(e, _mutated(ok, _set(prepared_slot=1))), 2, "crf_prepare_device was never called")]
+        for what, mutate, code, text in BAD_PARAMS:
+            for mode, eng, call, flags in (("field", plain, field, 0), ("field, device", plain, field_device, 0),
+                                           ("symmetric", two, field, sym), ("symmetric, device", two, field_device, sym),
+                                           ("requests", plain, requests, 0), ("requests, two fields", two, requests, query_sec)):
+                p = _mutated(_valid_params(flags=flags), mutate)
+                table.append((f"{mode}: {what}", eng, lambda e, call=call, p=p: call(e, p), code, text))
+        table += [
+            ("CRF_FLAG_SYMMETRIC without secondary members", plain, lambda e: field(e, _valid_params(flags=sym)), 2, "secondary"),
+            ("CRF_FLAG_REFERENCE_FROM_SECONDARY without secondary members", plain,
+             lambda e: field(e, _valid_params(flags=ref_sec)), 2, "secondary"),
+            ("CRF_FLAG_QUERY_FROM_SECONDARY without secondary members", plain,
+             lambda e: requests(e, _valid_params(flags=query_sec)), 2, "secondary"),
+            ("crf_prepare_device with CRF_FLAG_SYMMETRIC", two, lambda e: prepare(e, _valid_params(flags=sym), 0), 1,
+             "no reference-side preparation"),
+            ("prepared_slot -1", plain, lambda e: field_device(e, _mutated(ok, _set(prepared_slot=-1))), 1,
+             f"prepared_slot -1 outside [0,{slots}]"),
+            (f"prepared_slot {slots + 1}", plain, lambda e: field_device(e, _mutated(ok, _set(prepared_slot=slots + 1))), 1,
+             f"prepared_slot {slots + 1} outside [0,{slots}]"),
+            ("crf_prepare_device slot -1", plain, lambda e: prepare(e, ok, -1), 1, f"slot -1 outside [0,{slots})"),
+            (f"crf_prepare_device slot {slots}", plain, lambda e: prepare(e, ok, slots), 1, f"slot {slots} outside [0,{slots})"),
+        ]
+        for name, call in (("crf_prepare_rows_device", prepare_rows), ("crf_compute_prepared_device", compute_prepared)):
+            for first, count in ((-1, 1), (slots - 1, 2), (slots, 1), (0, -1)):
+                table.append((f"{name} slots {first}+{count}", plain, lambda e, call=call, f=first, k=count: call(e, ok, f, k), 1,
+                              f"slots [{first}, {first + count}) outside [0, {slots})"))
+        table += [
+            ("ensemble stat: null output", plain, lambda e: lib.crf_compute_ensemble_stat(e._ctx, 0, null_f), 1, "null output"),
+            ("ensemble stat, device: null output", plain,
+             lambda e: lib.crf_compute_ensemble_stat_device(e._ctx, 0, null_v, null_v), 1, "null output"),
+            ("set predicate: null output", plain, lambda e: lib.crf_compute_set_predicate(e._ctx, 0, 0.0, 0, cs, null_f), 1,
+             "null output"),
+            ("set predicate, device: null output", plain,
+             lambda e: lib.crf_compute_set_predicate_device(e._ctx, 0, 0.0, 0, cs, null_v, null_v), 1, "null output"),
+            ("DKL: null output", plain, lambda e: lib.crf_compute_dkl(e._ctx, 0, 20, 2, null_f), 1, "null output"),
+            ("DKL, device: null output", plain, lambda e: lib.crf_compute_dkl_device(e._ctx, 0, 20, 2, null_v, null_v), 1,
+             "null output"),
+        ]
+        for stat in (-1, 2):
+            table += [(f"ensemble statistic {stat}", plain, lambda e, s=stat: lib.crf_compute_ensemble_stat(e._ctx, s, host_p), 1,
+                       f"unknown ensemble statistic {stat}"),
+                      (f"ensemble statistic {stat}, device", plain,
+                       lambda e, s=stat: lib.crf_compute_ensemble_stat_device(e._ctx, s, dev_p, null_v), 1,
+                       f"unknown ensemble statistic {stat}")]
+        for op in (-1, 6):
+            table += [(f"comparison operator {op}", plain,
+                       lambda e, o=op: lib.crf_compute_set_predicate(e._ctx, o, 0.0, 0, cs, host_p), 1,
+                       f"unknown comparison operator {op}"),
+                      (f"comparison operator {op}, device", plain,
+                       lambda e, o=op: lib.crf_compute_set_predicate_device(e._ctx, o, 0.0, 0, cs, dev_p, null_v), 1,
+                       f"unknown comparison operator {op}")]
+        for est in (-1, 2):
+            table += [(f"DKL estimator {est}", plain, lambda e, d=est: lib.crf_compute_dkl(e._ctx, d, 20, 2, host_p), 1,
+                       f"unknown DKL estimator {est}"),
+                      (f"DKL estimator {est}, device", plain,
+                       lambda e, d=est: lib.crf_compute_dkl_device(e._ctx, d, 20, 2, dev_p, null_v), 1,
+                       f"unknown DKL estimator {est}")]
+
+        # the table's own valid starting points are valid: no row fails for a second reason
+        assert field(plain, ok) == 0 and field(two, _valid_params(flags=sym)) == 0 and requests(plain, ok) == 0
+
+        wrong = []
+        for what, eng, call, code, text in table:
+            rc = call(eng)
+            message = (lib.crf_last_error(eng._ctx) or b"").decode()
+            print(f"cs={cs} {what}: status {rc}, \"{message}\"")
+            if rc != code or text not in message:
+                wrong.append((what, rc, message, code, text))
+            if not np.isfinite(eng.compute(Measure.PEARSON, (1, 1, 1))).all():
+                wrong.append((what, "the context no longer computes a finite Pearson field"))
+        assert not wrong, wrong
+    finally:
+        plain.close()
+        two.close()
+
