@@ -950,44 +950,28 @@ hipError_t launch_generic(const float* const* d_members, int cs, size_t num_voxe
     }
     if (!ref.run()) return hipGetLastError();
     const size_t tiles = (num_voxels + 63) / 64;
-    const char* force_tile = getenv("CRF_RANK_TILE");  // tuning: keep the LDS-tile kernel wherever the tile fits
-    if ((a.measure == 1 || a.measure == 2) &&
-        (tile_bytes(cs) > kLdsTileLimit || !(force_tile && *force_tile == '1'))) {
-        const unsigned dblocks = unsigned(tiles < size_t(kDirectBlocks) ? tiles : size_t(kDirectBlocks));
+    if (a.measure == 1 || a.measure == 2) {
+        // Spearman / Kendall: the direct-read counting kernel.  At 129..256 members the pair kernels go first (two sorted
+        // chunks merged through LDS, kernels_rank.hip) and the counting kernel only walks the voxels they deferred
+        // (ties); CRF_RANK_PAIR=0: the counting kernel for every voxel.
         if (a.measure == 1 && !d_workspace) return hipErrorInvalidValue;
-        if (ev_begin) (void)hipEventRecord(ev_begin, s);
-        // Spearman at 129..256 members: two sorted chunks merged through LDS (kernels_rank.hip: spearman_pair_kernel),
-        // then this file's counting kernel over the voxels it deferred (ties); Kendall the same (kendall_pair_kernel).
-        // CRF_RANK_PAIR=0: counting kernel for all.
         const char* pair_env = getenv("CRF_RANK_PAIR");
-        if (a.measure == 1 && !(pair_env && *pair_env == '0') &&
-            launch_spearman_pair(d_members, d_prep, d_out, num_voxels, cs, d_todo, s)) {
-            hipLaunchKernelGGL((direct_rank_kernel<1, true>), dim3(dblocks < 1024u ? dblocks : 1024u), dim3(64), 0, s,
-                               d_members, static_cast<const void*>(d_prep), d_out, num_voxels, cs,
-                               reinterpret_cast<uint16_t*>(d_workspace), static_cast<const uint32_t*>(d_todo));
-            if (ev_end) (void)hipEventRecord(ev_end, s);
-            if (info) info->kernel_name = "spearman_pair_kernel";
-            return hipGetLastError();
-        }
-        if (a.measure == 2 && !(pair_env && *pair_env == '0') &&
-            launch_kendall_pair(d_members, reinterpret_cast<const int*>(d_prep), d_out, num_voxels, cs, d_todo, s)) {
-            hipLaunchKernelGGL((direct_rank_kernel<2, true>), dim3(dblocks < 1024u ? dblocks : 1024u), dim3(64), 0, s,
-                               d_members, static_cast<const void*>(d_prep), d_out, num_voxels, cs,
-                               reinterpret_cast<uint16_t*>(d_workspace), static_cast<const uint32_t*>(d_todo));
-            if (ev_end) (void)hipEventRecord(ev_end, s);
-            if (info) info->kernel_name = "kendall_pair_kernel";
-            return hipGetLastError();
-        }
-        if (a.measure == 1)
-            hipLaunchKernelGGL((direct_rank_kernel<1, false>), dim3(dblocks), dim3(64), 0, s, d_members,
-                               static_cast<const void*>(d_prep), d_out, num_voxels, cs,
-                               reinterpret_cast<uint16_t*>(d_workspace), static_cast<const uint32_t*>(nullptr));
-        else
-            hipLaunchKernelGGL((direct_rank_kernel<2, false>), dim3(dblocks), dim3(64), 0, s, d_members,
-                               static_cast<const void*>(d_prep), d_out, num_voxels, cs,
-                               reinterpret_cast<uint16_t*>(d_workspace), static_cast<const uint32_t*>(nullptr));
+        const bool try_pair = !(pair_env && *pair_env == '0');
+        if (ev_begin) (void)hipEventRecord(ev_begin, s);
+        const bool paired =
+            try_pair && (a.measure == 1 ? launch_spearman_pair(d_members, d_prep, d_out, num_voxels, cs, d_todo, s)
+                                        : launch_kendall_pair(d_members, reinterpret_cast<const int*>(d_prep), d_out,
+                                                              num_voxels, cs, d_todo, s));
+        const auto kernel = a.measure == 1 ? (paired ? direct_rank_kernel<1, true> : direct_rank_kernel<1, false>)
+                                           : (paired ? direct_rank_kernel<2, true> : direct_rank_kernel<2, false>);
+        const size_t max_blocks = paired ? 1024 : size_t(kDirectBlocks);  // the list is short: grid-stride over it
+        hipLaunchKernelGGL(kernel, dim3(unsigned(tiles < max_blocks ? tiles : max_blocks)), dim3(64), 0, s, d_members,
+                           static_cast<const void*>(d_prep), d_out, num_voxels, cs,
+                           reinterpret_cast<uint16_t*>(d_workspace),
+                           static_cast<const uint32_t*>(paired ? d_todo : nullptr));
         if (ev_end) (void)hipEventRecord(ev_end, s);
-        if (info) info->kernel_name = "direct_rank_kernel";
+        if (info)
+            info->kernel_name = !paired ? "direct_rank_kernel" : a.measure == 1 ? "spearman_pair_kernel" : "kendall_pair_kernel";
         return hipGetLastError();
     }
     const unsigned blocks = unsigned(tiles < size_t(kGenericBlocks) ? tiles : size_t(kGenericBlocks));

@@ -1226,8 +1226,9 @@ __device__ __forceinline__ int32_t chunk_inversions(const composite_t (&a)[CH], 
     return inv;
 }
 
-// CHB, NPAD: see spearman_split_kernel; the preparation tables use the stride NPAD = pad_pow2(cs)
-template <int CH, bool EXACT, int MIN_WAVES, int CHB = CH, int NPAD = 2 * CH>
+// CHB, NPAD: see spearman_split_kernel; the preparation tables use the stride NPAD = pad_pow2(cs).  Chunk B is always
+// guarded (no unguarded form as spearman_split_kernel's EXACT: it measured slower for every member count).
+template <int CH, int MIN_WAVES, int CHB = CH, int NPAD = 2 * CH>
 __global__ __launch_bounds__(64, MIN_WAVES) void kendall_split_kernel(const float* const* __restrict__ members,
                                                                       const int* __restrict__ prep,
                                                                       float* __restrict__ out, size_t num_voxels,
@@ -1275,7 +1276,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_split_kernel(const floa
     order_after(tie_min, byte_offset_b);
     {
         composite_t b[CHB];
-        load_chunk<CHB, EXACT, true, SURE_B>(b, members, prep, CH, cs, bytes, byte_offset_b);
+        load_chunk<CHB, false, true, SURE_B>(b, members, prep, CH, cs, bytes, byte_offset_b);
         __builtin_amdgcn_sched_barrier(0);
         SortNet<CHB>::sort(b);
         pin_array(b);  // the network ends here (crf_device.h)
@@ -1284,7 +1285,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_split_kernel(const floa
         constexpr int G = 4;  // see spearman_split_kernel
 #pragma unroll
         for (int p0 = 0; p0 < CHB; p0 += G) {
-            const bool guarded = !EXACT && p0 >= SURE_B;  // compile time per batch
+            const bool guarded = p0 >= SURE_B;  // compile time per batch
             if (!guarded || p0 + G <= nB) {
                 uint32_t key[G], less[G];
 #pragma unroll
@@ -1294,7 +1295,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_split_kernel(const floa
                     if (p > 0) tie_min = min(tie_min, key[g] ^ prev);
                     if (p > 0) tie_or |= key[g] ^ prev;
                     if (p == 0) is_nan |= key[g] < 0x007FFFFFu;
-                    if (EXACT ? p == CHB - 1 : guarded) is_nan |= (EXACT || p == nB - 1) && key[g] > 0xFF800000u;
+                    if (guarded) is_nan |= p == nB - 1 && key[g] > 0xFF800000u;
                     prev = key[g];
                 }
                 lower_bound_col_batch<CH, G>(&keysA[lane], key, tie_min, less);
@@ -1316,7 +1317,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_split_kernel(const floa
                 }
             }
         }
-        discordant += chunk_inversions<CHB, SURE_B>(b, nB, EXACT);
+        discordant += chunk_inversions<CHB, SURE_B>(b, nB, false);
         // every member equal (a mask: whole regions of such voxels in real ensembles): n2 = n0, no discordant pair, and
         // with n1 = 0 (x ties went the other way above) tau = 0 / 0 -- no need to send the voxel to the exact kernel
         all_equal = tie_or == 0u && keysA[lane] == prev;
@@ -1337,156 +1338,6 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_split_kernel(const floa
     }
 }
 
-namespace {
-
-// tuning switches (tools/tune_pearson.py): CRF_RANK_SPLIT64=1 uses the split-sort kernels for 33..64 members too
-bool env_split64() {
-    const char* v = getenv("CRF_RANK_SPLIT64");
-    return v && *v == '1';
-}
-
-bool env_split64_default_on() {
-    const char* v = getenv("CRF_RANK_SPLIT64");
-    return !(v && *v == '0');
-}
-
-// CRF_RANK_EXACT=0 forces the guarded instantiations
-bool env_exact() {
-    const char* v = getenv("CRF_RANK_EXACT");
-    return !(v && *v == '0');
-}
-
-constexpr unsigned kTodoBlocks = 2048;  // grid of the list-walking pass (grid-stride over the deferred voxels)
-
-template <int N, int MIN_WAVES>
-void launch_spearman_n(const float* const* d_members, const float* d_prep, float* d_out, size_t num_voxels, int cs,
-                       hipStream_t s, const uint32_t* todo = nullptr) {
-    const unsigned blocks = todo ? kTodoBlocks : unsigned((num_voxels + 63) / 64);
-    const bool exact = cs == N && env_exact();
-#define CRF_LAUNCH_SPEARMAN(EX, LIST)                                                                                  \
-    hipLaunchKernelGGL((spearman_kernel<N, EX, MIN_WAVES, LIST>), dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out, \
-                       num_voxels, cs, todo)
-    if (todo) {
-        if (exact) CRF_LAUNCH_SPEARMAN(true, true); else CRF_LAUNCH_SPEARMAN(false, true);
-    } else {
-        if (exact) CRF_LAUNCH_SPEARMAN(true, false); else CRF_LAUNCH_SPEARMAN(false, false);
-    }
-#undef CRF_LAUNCH_SPEARMAN
-}
-
-template <int N, int MIN_WAVES>
-void launch_kendall_n(const float* const* d_members, const int* d_prep, float* d_out, size_t num_voxels, int cs,
-                      hipStream_t s, const uint32_t* todo = nullptr) {
-    const unsigned blocks = todo ? kTodoBlocks : unsigned((num_voxels + 63) / 64);
-    const bool exact = cs == N && env_exact();
-#define CRF_LAUNCH_KENDALL(EX, LIST)                                                                                  \
-    hipLaunchKernelGGL((kendall_kernel<N, EX, MIN_WAVES, LIST>), dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out, \
-                       num_voxels, cs, todo)
-    if (todo) {
-        if (exact) CRF_LAUNCH_KENDALL(true, true); else CRF_LAUNCH_KENDALL(false, true);
-    } else {
-        if (exact) CRF_LAUNCH_KENDALL(true, false); else CRF_LAUNCH_KENDALL(false, false);
-    }
-#undef CRF_LAUNCH_KENDALL
-}
-
-// split-sort launchers: chunk A = CH members, chunk B sorted by a CHB-network (CH < cs <= CH + CHB)
-template <int CH, int CHB, int WAVES>
-void launch_spearman_split(bool exact, const float* const* d_members, const float* d_prep, float* d_out,
-                           size_t num_voxels, int cs, hipStream_t s, uint32_t* d_todo) {
-    const unsigned blocks = unsigned((num_voxels + 63) / 64);
-    if (exact && cs == CH + CHB)
-        hipLaunchKernelGGL((spearman_split_kernel<CH, true, WAVES, CHB>), dim3(blocks), dim3(64), 0, s, d_members, d_prep,
-                           d_out, num_voxels, cs, d_todo);
-    else
-        hipLaunchKernelGGL((spearman_split_kernel<CH, false, WAVES, CHB>), dim3(blocks), dim3(64), 0, s, d_members,
-                           d_prep, d_out, num_voxels, cs, d_todo);
-}
-template <int CH, int CHB, int WAVES>
-void launch_kendall_split(bool exact, const float* const* d_members, const int* d_prep, float* d_out, size_t num_voxels,
-                          int cs, hipStream_t s, uint32_t* d_todo) {
-    const unsigned blocks = unsigned((num_voxels + 63) / 64);
-    if (exact && cs == CH + CHB)
-        hipLaunchKernelGGL((kendall_split_kernel<CH, true, WAVES, CHB, 2 * CH>), dim3(blocks), dim3(64), 0, s, d_members,
-                           d_prep, d_out, num_voxels, cs, d_todo);
-    else
-        hipLaunchKernelGGL((kendall_split_kernel<CH, false, WAVES, CHB, 2 * CH>), dim3(blocks), dim3(64), 0, s, d_members,
-                           d_prep, d_out, num_voxels, cs, d_todo);
-}
-
-int pad_pow2(int cs) { return cs <= 8 ? 8 : cs <= 16 ? 16 : cs <= 32 ? 32 : cs <= 64 ? 64 : 128; }
-
-int env_int(const char* name, int fallback) {
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : fallback;
-}
-bool env_flag(const char* name) { return env_int(name, 0) == 1; }
-
-// waves/SIMD the 64-member kernels are compiled for (register cap 512/256/168); CRF_RANK_WAVES overrides for tuning.
-int env_waves(int fallback) {
-    const char* v = getenv("CRF_RANK_WAVES");
-    return (v && *v) ? atoi(v) : fallback;
-}
-
-}  // namespace
-
-// 129..256 members: spearman_pair_kernel; the caller runs the counting kernel over d_todo afterwards (voxels with ties).
-bool launch_spearman_pair(const float* const* d_members, const float* d_prep, float* d_out, size_t num_voxels, int cs,
-                          uint32_t* d_todo, hipStream_t s) {
-    if (cs <= 128 || cs > 256 || !d_todo) return false;
-    (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-    const unsigned blocks = unsigned((num_voxels + 63) / 64);
-    const int n = ((cs + 1) / 2 + 7) / 8 * 8;  // chunk size: 2 n - 16 < cs <= 2 n
-#define CRF_LAUNCH_PAIR(NN)                                                                                             \
-    case NN:                                                                                                            \
-        hipLaunchKernelGGL((spearman_pair_kernel<NN, (NN > 112 ? 1 : 2)>), dim3(blocks), dim3(64), 0, s, d_members,     \
-                           d_prep, d_out,                                                                               \
-                           num_voxels, cs, d_todo);                                                                     \
-        break
-    switch (n) {
-        CRF_LAUNCH_PAIR(72);
-        CRF_LAUNCH_PAIR(80);
-        CRF_LAUNCH_PAIR(88);
-        CRF_LAUNCH_PAIR(96);
-        CRF_LAUNCH_PAIR(104);
-        CRF_LAUNCH_PAIR(112);
-        CRF_LAUNCH_PAIR(120);
-        CRF_LAUNCH_PAIR(128);
-        default: return false;
-    }
-#undef CRF_LAUNCH_PAIR
-    return true;
-}
-
-// 129..256 members: kendall_pair_kernel (prep: kendall_prep_kernel's tables with stride cs); the caller runs the counting
-// kernel over d_todo afterwards.  One wave per SIMD for the register budget: at two the kernel needs > 256 registers and
-// spills 0.3 KB to scratch, at one the overflow goes to AGPRs (LDS allows 3-5 waves per CU anyway).
-bool launch_kendall_pair(const float* const* d_members, const int* d_prep, float* d_out, size_t num_voxels, int cs,
-                         uint32_t* d_todo, hipStream_t s) {
-    if (cs <= 128 || cs > 256 || !d_todo) return false;
-    (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-    const unsigned blocks = unsigned((num_voxels + 63) / 64);
-    const int n = ((cs + 1) / 2 + 7) / 8 * 8;
-#define CRF_LAUNCH_PAIR(NN)                                                                                             \
-    case NN:                                                                                                            \
-        hipLaunchKernelGGL((kendall_pair_kernel<NN, 1>), dim3(blocks), dim3(64), 0, s, d_members,                       \
-                           d_prep, d_out, num_voxels, cs, d_todo);                                                      \
-        break
-    switch (n) {
-        CRF_LAUNCH_PAIR(72);
-        CRF_LAUNCH_PAIR(80);
-        CRF_LAUNCH_PAIR(88);
-        CRF_LAUNCH_PAIR(96);
-        CRF_LAUNCH_PAIR(104);
-        CRF_LAUNCH_PAIR(112);
-        CRF_LAUNCH_PAIR(120);
-        CRF_LAUNCH_PAIR(128);
-        default: return false;
-    }
-#undef CRF_LAUNCH_PAIR
-    return true;
-}
-
 void launch_spearman_prep(const RefSource& ref, const float* const* d_members, int cs, float* d_prep, hipStream_t s) {
     hipLaunchKernelGGL(spearman_prep_kernel, dim3(1), dim3(256), size_t(2 * cs) * sizeof(float), s, ref, d_members, cs,
                        d_prep);
@@ -1498,248 +1349,248 @@ void launch_kendall_prep(const RefSource& ref, const float* const* d_members, in
                        d_prep);
 }
 
+// Host dispatch.  Which kernel answers which member count (tables: DESIGN.md, "Rank kernels: dispatch"):
+//   spearman_plan / kendall_plan                 2..128 members: {first pass, list pass, reported name}
+//   launch_spearman_pair / launch_kendall_pair   129..256 members (the caller, launch_generic, runs the list pass)
+// A first pass defers the voxels it cannot answer (ties) to the todo list {count, voxel indices...}; the list pass is
+// the monolithic kernel of the padded size in its LIST form.  A plan without a first pass runs the monolithic kernel
+// over every voxel.  Chunk sizes are multiples of 8 (sortnet.inc has a network for each).
+namespace {
+
+constexpr unsigned kTodoBlocks = 2048;  // grid of the list pass (grid-stride over the deferred voxels)
+
+template <class P>  // P: float (Spearman's prep) or int (Kendall's)
+using FirstKernel = void (*)(const float* const*, const P*, float*, size_t, int, uint32_t*);
+template <class P>
+using ListKernel = void (*)(const float* const*, const P*, float*, size_t, int, const uint32_t*);
+
+template <class P>
+struct RankPlan {
+    FirstKernel<P> first;  // null: `list` is the non-LIST monolithic kernel and runs alone
+    ListKernel<P> list;
+    const char* name;
+};
+
+int round_up_8(int n) { return (n + 7) / 8 * 8; }
+
+// CRF_RANK_U32=0: Spearman at 33..128 members with the 64-bit-composite kernels instead of the u32 network.  Read per
+// call (tests set it after the library is loaded).
+bool u32_network_enabled() {
+    const char* v = getenv("CRF_RANK_U32");
+    return !(v && *v && atoi(v) == 0);
+}
+
+// EXACT (cs == N: no pad slots) or guarded instantiation
+template <int N, int WAVES, bool LIST>
+ListKernel<float> spearman_mono(int cs) {
+    return cs == N ? spearman_kernel<N, true, WAVES, LIST> : spearman_kernel<N, false, WAVES, LIST>;
+}
+template <int N, int WAVES, bool LIST>
+ListKernel<int> kendall_mono(int cs) {
+    return cs == N ? kendall_kernel<N, true, WAVES, LIST> : kendall_kernel<N, false, WAVES, LIST>;
+}
+template <int N>
+FirstKernel<float> spearman_u32(int cs) {
+    return cs == N ? spearman_u32_kernel<N, 2, true> : spearman_u32_kernel<N, 2, false>;
+}
+template <int CHB>  // 64 + CHB members: unguarded when cs fills chunk B
+FirstKernel<float> spearman_split64(int cs) {
+    return cs == 64 + CHB ? spearman_split_kernel<64, true, 2, CHB> : spearman_split_kernel<64, false, 2, CHB>;
+}
+
+// 33..128 members, one network over 32-bit composites padded to a multiple of 8.  256^3, against the split-sort
+// kernels: 40 members 0.77 -> 0.70 ms, 64: 1.22 -> 1.17, 72: 1.73 -> 1.35, 96: 2.60 -> 2.02, 128: 3.50 -> 2.72.
+FirstKernel<float> spearman_u32_first(int cs) {
+    switch (round_up_8(cs)) {
+        case 40: return spearman_u32<40>(cs);
+        case 48: return spearman_u32<48>(cs);
+        case 56: return spearman_u32<56>(cs);
+        case 64: return spearman_u32<64>(cs);
+        case 72: return spearman_u32<72>(cs);
+        case 80: return spearman_u32<80>(cs);
+        case 88: return spearman_u32<88>(cs);
+        case 96: return spearman_u32<96>(cs);
+        case 104: return spearman_u32<104>(cs);
+        case 112: return spearman_u32<112>(cs);
+        case 120: return spearman_u32<120>(cs);
+        default: return spearman_u32<128>(cs);
+    }
+}
+
+// split-sort first pass: chunk A = CH members, chunk B = the rest, sorted by the network of CHB = cs - CH rounded up to 8
+FirstKernel<float> spearman_split_first(int cs) {
+    if (cs <= 32) return cs <= 24 ? spearman_split_kernel<16, false, 4, 8> : spearman_split_kernel<16, false, 4, 16>;
+    if (cs <= 64) {
+        switch (round_up_8(cs - 32)) {
+            case 8: return spearman_split_kernel<32, false, 4, 8>;
+            case 16: return spearman_split_kernel<32, false, 4, 16>;
+            case 24: return spearman_split_kernel<32, false, 4, 24>;
+            default: return spearman_split_kernel<32, false, 4, 32>;
+        }
+    }
+    switch (round_up_8(cs - 64)) {
+        case 8: return spearman_split64<8>(cs);
+        case 16: return spearman_split64<16>(cs);
+        case 24: return spearman_split64<24>(cs);
+        case 32: return spearman_split64<32>(cs);
+        case 40: return spearman_split64<40>(cs);
+        case 48: return spearman_split64<48>(cs);
+        // 56 / 64: the unguarded instantiations spill (120 members: 3.96 vs 3.78 ms, 128: 4.83 vs 4.10 ms)
+        case 56: return spearman_split_kernel<64, false, 2, 56>;
+        default: return spearman_split_kernel<64, false, 2, 64>;
+    }
+}
+
+RankPlan<float> spearman_plan(int cs, bool u32) {
+    if (cs <= 8) return {nullptr, spearman_mono<8, 4, false>(cs), "spearman_kernel"};
+    if (cs <= 16) return {nullptr, spearman_mono<16, 4, false>(cs), "spearman_kernel"};
+    // 32 and 64 members exactly fill the monolithic kernel, which then beats the split-sort one (256^3: 32 members
+    // 0.62-0.66 vs 0.65 ms, 64: 1.75 vs 1.87-1.96 ms); with pads it is 2-4 times slower (24 members: 1.2-2.0 vs 0.56 ms)
+    if (cs < 32) return {spearman_split_first(cs), spearman_kernel<32, false, 4, true>, "spearman_split_kernel"};
+    if (cs == 32) return {nullptr, spearman_kernel<32, true, 4, false>, "spearman_kernel"};
+    if (u32)
+        return {spearman_u32_first(cs), cs <= 64 ? spearman_mono<64, 2, true>(cs) : spearman_mono<128, 1, true>(cs),
+                "spearman_u32_kernel"};
+    if (cs < 64) return {spearman_split_first(cs), spearman_kernel<64, false, 2, true>, "spearman_split_kernel"};
+    if (cs == 64) return {nullptr, spearman_kernel<64, true, 2, false>, "spearman_kernel"};
+    return {spearman_split_first(cs), spearman_mono<128, 1, true>(cs), "spearman_split_kernel"};
+}
+
+// Split-sort from 17 members on, every chunk B guarded: 256^3, against the monolithic kernel: 32 members 0.55 vs
+// 0.63-1.23 ms, 64: 1.49 vs 2.64, 128: 4.8 vs 13.9-27.7 (the guarded form compiles to 226 VGPRs without scratch).
+// The prep tables have the stride of the padded size, 2 * CH.
+FirstKernel<int> kendall_split_first(int cs) {
+    if (cs <= 32) return cs <= 24 ? kendall_split_kernel<16, 4, 8, 32> : kendall_split_kernel<16, 4, 16, 32>;
+    if (cs <= 64) {
+        switch (round_up_8(cs - 32)) {
+            case 8: return kendall_split_kernel<32, 4, 8, 64>;
+            case 16: return kendall_split_kernel<32, 4, 16, 64>;
+            case 24: return kendall_split_kernel<32, 4, 24, 64>;
+            default: return kendall_split_kernel<32, 4, 32, 64>;
+        }
+    }
+    switch (round_up_8(cs - 64)) {
+        case 8: return kendall_split_kernel<64, 2, 8, 128>;
+        case 16: return kendall_split_kernel<64, 2, 16, 128>;
+        case 24: return kendall_split_kernel<64, 2, 24, 128>;
+        case 32: return kendall_split_kernel<64, 2, 32, 128>;
+        case 40: return kendall_split_kernel<64, 2, 40, 128>;
+        case 48: return kendall_split_kernel<64, 2, 48, 128>;
+        case 56: return kendall_split_kernel<64, 2, 56, 128>;
+        default: return kendall_split_kernel<64, 2, 64, 128>;
+    }
+}
+
+RankPlan<int> kendall_plan(int cs) {
+    if (cs <= 8) return {nullptr, kendall_mono<8, 4, false>(cs), "kendall_kernel"};
+    if (cs <= 16) return {nullptr, kendall_mono<16, 4, false>(cs), "kendall_kernel"};
+    ListKernel<int> list = cs <= 32   ? kendall_mono<32, 4, true>(cs)
+                           : cs <= 64 ? kendall_mono<64, 1, true>(cs)
+                                      : kendall_mono<128, 1, true>(cs);
+    return {kendall_split_first(cs), list, "kendall_split_kernel"};
+}
+
+// Clears the list counter and launches a first pass: one lane per voxel, voxels with ties go to the list.
+template <class P>
+void launch_first_pass(FirstKernel<P> first, const float* const* d_members, const P* d_prep, float* d_out,
+                       size_t num_voxels, int cs, uint32_t* d_todo, hipStream_t s) {
+    (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
+    hipLaunchKernelGGL(first, dim3(unsigned((num_voxels + 63) / 64)), dim3(64), 0, s, d_members, d_prep, d_out,
+                       num_voxels, cs, d_todo);
+}
+
+// What launch_spearman and launch_kendall share once the reference side is prepared (2..128 members): first pass and
+// list pass, or the monolithic kernel alone; event records; the reported name.
+template <class P>
+hipError_t launch_plan(const RankPlan<P>& plan, const float* const* d_members, const P* d_prep, float* d_out,
+                       size_t num_voxels, int cs, uint32_t* d_todo, hipStream_t s, hipEvent_t ev_begin,
+                       hipEvent_t ev_end, LaunchInfo* info) {
+    if (ev_begin) (void)hipEventRecord(ev_begin, s);
+    if (plan.first) launch_first_pass(plan.first, d_members, d_prep, d_out, num_voxels, cs, d_todo, s);
+    const unsigned blocks = plan.first ? kTodoBlocks : unsigned((num_voxels + 63) / 64);
+    hipLaunchKernelGGL(plan.list, dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out, num_voxels, cs,
+                       static_cast<const uint32_t*>(plan.first ? d_todo : nullptr));
+    if (ev_end) (void)hipEventRecord(ev_end, s);
+    if (info) info->kernel_name = plan.name;
+    return hipGetLastError();
+}
+
+// One member: every rank vector is (1), the coefficient is 1 by the reference's convention.
+hipError_t launch_single_member(const RefSource& ref, float* d_out, size_t num_voxels, hipStream_t s,
+                                hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    if (!ref.run()) return hipSuccess;
+    if (ev_begin) (void)hipEventRecord(ev_begin, s);
+    hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
+    if (ev_end) (void)hipEventRecord(ev_end, s);
+    if (info) info->kernel_name = "fill_kernel";
+    return e;
+}
+
+int pad_pow2(int cs) { return cs <= 8 ? 8 : cs <= 16 ? 16 : cs <= 32 ? 32 : cs <= 64 ? 64 : 128; }
+
+}  // namespace
+
+// 129..256 members: two sorted chunks of N = half the member count rounded up to 8 (2 N - 16 < cs <= 2 N), merged
+// through LDS.  The caller runs the counting kernel over d_todo afterwards (voxels with ties).
+bool launch_spearman_pair(const float* const* d_members, const float* d_prep, float* d_out, size_t num_voxels, int cs,
+                          uint32_t* d_todo, hipStream_t s) {
+    if (cs <= 128 || cs > 256 || !d_todo) return false;
+    FirstKernel<float> k = nullptr;
+    switch (round_up_8((cs + 1) / 2)) {  // two waves per SIMD up to 112, one beyond (registers)
+        case 72: k = spearman_pair_kernel<72, 2>; break;
+        case 80: k = spearman_pair_kernel<80, 2>; break;
+        case 88: k = spearman_pair_kernel<88, 2>; break;
+        case 96: k = spearman_pair_kernel<96, 2>; break;
+        case 104: k = spearman_pair_kernel<104, 2>; break;
+        case 112: k = spearman_pair_kernel<112, 2>; break;
+        case 120: k = spearman_pair_kernel<120, 1>; break;
+        default: k = spearman_pair_kernel<128, 1>; break;
+    }
+    launch_first_pass(k, d_members, d_prep, d_out, num_voxels, cs, d_todo, s);
+    return true;
+}
+
+// 129..256 members: kendall_pair_kernel (prep: kendall_prep_kernel's tables with stride cs); the caller runs the counting
+// kernel over d_todo afterwards.  One wave per SIMD for the register budget: at two the kernel needs > 256 registers and
+// spills 0.3 KB to scratch, at one the overflow goes to AGPRs (LDS allows 3-5 waves per CU anyway).
+bool launch_kendall_pair(const float* const* d_members, const int* d_prep, float* d_out, size_t num_voxels, int cs,
+                         uint32_t* d_todo, hipStream_t s) {
+    if (cs <= 128 || cs > 256 || !d_todo) return false;
+    FirstKernel<int> k = nullptr;
+    switch (round_up_8((cs + 1) / 2)) {
+        case 72: k = kendall_pair_kernel<72, 1>; break;
+        case 80: k = kendall_pair_kernel<80, 1>; break;
+        case 88: k = kendall_pair_kernel<88, 1>; break;
+        case 96: k = kendall_pair_kernel<96, 1>; break;
+        case 104: k = kendall_pair_kernel<104, 1>; break;
+        case 112: k = kendall_pair_kernel<112, 1>; break;
+        case 120: k = kendall_pair_kernel<120, 1>; break;
+        default: k = kendall_pair_kernel<128, 1>; break;
+    }
+    launch_first_pass(k, d_members, d_prep, d_out, num_voxels, cs, d_todo, s);
+    return true;
+}
+
 hipError_t launch_spearman(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref, float* d_prep,
                            uint32_t* d_todo, float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
                            LaunchInfo* info) {
-    bool split = false, u32 = false;
-    if (cs == 1) {
-        if (!ref.run()) return hipSuccess;
-        if (ev_begin) (void)hipEventRecord(ev_begin, s);
-        hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
-        if (ev_end) (void)hipEventRecord(ev_end, s);
-        if (info) info->kernel_name = "fill_kernel";
-        return e;
-    }
+    if (cs == 1) return launch_single_member(ref, d_out, num_voxels, s, ev_begin, ev_end, info);
+    if (cs > 16 && !d_todo) return hipErrorInvalidValue;
     if (ref.prepare()) launch_spearman_prep(ref, d_members, cs, d_prep, s);
     if (!ref.run()) return hipGetLastError();
-    if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    switch (pad_pow2(cs)) {
-        case 8: launch_spearman_n<8, 4>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-        case 16: launch_spearman_n<16, 4>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-        case 32:
-            // measured at 256^3: cs = 32: monolithic unguarded 0.62-0.66 ms, split 0.65 ms; cs = 24: monolithic guarded
-            // 1.2-2.0 ms, split 0.56 ms; cs = 20: 1.2-2.1 ms vs 0.49 ms
-            if (d_todo && cs > 16 && (cs < 32 || env_flag("CRF_RANK_SPLIT32"))) {
-                (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-                const unsigned blocks = unsigned((num_voxels + 63) / 64);
-                if (cs <= 24)
-                    hipLaunchKernelGGL((spearman_split_kernel<16, false, 4, 8>), dim3(blocks), dim3(64), 0, s, d_members,
-                                       d_prep, d_out, num_voxels, cs, d_todo);
-                else
-                    hipLaunchKernelGGL((spearman_split_kernel<16, false, 4, 16>), dim3(blocks), dim3(64), 0, s, d_members,
-                                       d_prep, d_out, num_voxels, cs, d_todo);
-                launch_spearman_n<32, 4>(d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                split = true;
-                break;
-            }
-            switch (env_int("CRF_RANK_WAVES32", 4)) {
-                case 2: launch_spearman_n<32, 2>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-                case 3: launch_spearman_n<32, 3>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-                default: launch_spearman_n<32, 4>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-            }
-            break;
-        case 64:
-            // 33..64 members: the u32 network too (256^3: 40 members 0.77 -> 0.70 ms, 48: 0.95 -> 0.85, 56: 1.16 -> 1.02,
-            // 64: 1.22 -> 1.17, 33: unchanged); CRF_RANK_U32=0 keeps the 64-bit-composite kernels
-            if (d_todo && cs > 32 && env_int("CRF_RANK_U32", 1) != 0) {
-                (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-                const unsigned blocks = unsigned((num_voxels + 63) / 64);
-#define CRF_LAUNCH_U32_SMALL(NN)                                                                                          \
-    if (cs == NN)                                                                                                        \
-        hipLaunchKernelGGL((spearman_u32_kernel<NN, 2, true>), dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out,   \
-                           num_voxels, cs, d_todo);                                                                     \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((spearman_u32_kernel<NN, 2, false>), dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out,  \
-                           num_voxels, cs, d_todo)
-                if (cs <= 40) { CRF_LAUNCH_U32_SMALL(40); }
-                else if (cs <= 48) { CRF_LAUNCH_U32_SMALL(48); }
-                else if (cs <= 56) { CRF_LAUNCH_U32_SMALL(56); }
-                else { CRF_LAUNCH_U32_SMALL(64); }
-#undef CRF_LAUNCH_U32_SMALL
-                launch_spearman_n<64, 2>(d_members, d_prep, d_out, num_voxels, cs, s, d_todo);  // voxels with ties
-                u32 = true;
-                break;
-            }
-            // measured at 256^3 (profiles/tuning_r01.md): cs = 64: monolithic unguarded 1.75 ms vs split 1.87-1.96 ms;
-            // cs = 48: monolithic guarded 5.26 ms vs split 1.65 ms; cs = 40: 5.45 ms vs 1.43 ms
-            if (d_todo && cs > 32 && (cs < 64 || env_split64())) {
-                (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-                const bool exact = env_exact() && getenv("CRF_RANK_EXACT");
-                if (cs <= 40)  // chunk B sorted by the smallest network of a multiple of 8 elements that holds it
-                    launch_spearman_split<32, 8, 4>(exact, d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 48)
-                    launch_spearman_split<32, 16, 4>(exact, d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 56)
-                    launch_spearman_split<32, 24, 4>(exact, d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else
-                    launch_spearman_split<32, 32, 4>(exact, d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                launch_spearman_n<64, 2>(d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                split = true;
-                break;
-            }
-            switch (env_waves(2)) {
-                case 1: launch_spearman_n<64, 1>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-                case 3: launch_spearman_n<64, 3>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-                default: launch_spearman_n<64, 2>(d_members, d_prep, d_out, num_voxels, cs, s); break;
-            }
-            break;
-        default:
-            // measured at 256^3 x 128 (profiles/tuning_r01.md): split 5.1 ms (unguarded) / 7.4 ms (guarded) vs
-            // monolithic 7.5 ms / 19 ms
-            if (d_todo && env_waves(2) != 0) {
-                (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-                const bool wide_exact = env_exact() && getenv("CRF_RANK_EXACT");  // only on request
-                const unsigned blocks = unsigned((num_voxels + 63) / 64);
-#define CRF_LAUNCH_U32(NN)                                                                                               \
-    if (cs == NN)                                                                                                        \
-        hipLaunchKernelGGL((spearman_u32_kernel<NN, 2, true>), dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out,   \
-                           num_voxels, cs, d_todo);                                                                     \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((spearman_u32_kernel<NN, 2, false>), dim3(blocks), dim3(64), 0, s, d_members, d_prep, d_out,  \
-                           num_voxels, cs, d_todo)
-                // One network over 32-bit composites (spearman_u32_kernel, padded to a multiple of 8): 256^3, split-sort ->
-                // u32 network: 72 members 1.73 -> 1.35 ms, 80: 1.89 -> 1.52, 96: 2.60 -> 2.02, 100: 2.77 -> 2.24, 112: 3.08
-                // -> 2.39, 128: 3.50 -> 2.72; 512^3 x 128 (BASELINE configs[3]) 27.6 -> 21.5 ms, bit-identical fields.
-                // CRF_RANK_U32=0 keeps the split-sort kernels.
-                const int u32_env = env_int("CRF_RANK_U32", -1);
-                if (cs > 64 && u32_env != 0) {
-                    if (cs <= 72) { CRF_LAUNCH_U32(72); }
-                    else if (cs <= 80) { CRF_LAUNCH_U32(80); }
-                    else if (cs <= 88) { CRF_LAUNCH_U32(88); }
-                    else if (cs <= 96) { CRF_LAUNCH_U32(96); }
-                    else if (cs <= 104) { CRF_LAUNCH_U32(104); }
-                    else if (cs <= 112) { CRF_LAUNCH_U32(112); }
-                    else if (cs <= 120) { CRF_LAUNCH_U32(120); }
-                    else { CRF_LAUNCH_U32(128); }
-                    u32 = true;
-                } else
-#undef CRF_LAUNCH_U32
-                if (cs <= 72)
-                    launch_spearman_split<64, 8, 2>(env_exact(), d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 80)
-                    launch_spearman_split<64, 16, 2>(env_exact(), d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 88)  // merge-exchange networks exist for any size
-                    launch_spearman_split<64, 24, 2>(env_exact(), d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 96)
-                    launch_spearman_split<64, 32, 2>(env_exact(), d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 104)
-                    launch_spearman_split<64, 40, 2>(env_exact(), d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 112)
-                    launch_spearman_split<64, 48, 2>(env_exact(), d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 120)  // 56 / 64: the unguarded instantiations spill (120: 3.96 vs 3.78 ms, 128: 4.83 vs 4.10 ms)
-                    launch_spearman_split<64, 56, 2>(wide_exact, d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                else
-                    launch_spearman_split<64, 64, 2>(wide_exact, d_members, d_prep, d_out, num_voxels, cs, s, d_todo);
-                launch_spearman_n<128, 1>(d_members, d_prep, d_out, num_voxels, cs, s, d_todo);  // voxels with ties
-                split = true;
-            } else {
-                launch_spearman_n<128, 1>(d_members, d_prep, d_out, num_voxels, cs, s);
-            }
-            break;
-    }
-    if (ev_end) (void)hipEventRecord(ev_end, s);
-    if (info) info->kernel_name = u32 ? "spearman_u32_kernel" : split ? "spearman_split_kernel" : "spearman_kernel";
-    return hipGetLastError();
+    return launch_plan<float>(spearman_plan(cs, u32_network_enabled()), d_members, d_prep, d_out, num_voxels, cs, d_todo,
+                              s, ev_begin, ev_end, info);
 }
 
 hipError_t launch_kendall(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref, float* d_prep,
                           uint32_t* d_todo, float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
                           LaunchInfo* info) {
-    bool split = false;
-    if (cs == 1) {
-        if (!ref.run()) return hipSuccess;
-        if (ev_begin) (void)hipEventRecord(ev_begin, s);
-        hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
-        if (ev_end) (void)hipEventRecord(ev_end, s);
-        if (info) info->kernel_name = "fill_kernel";
-        return e;
-    }
-    const int n_pad = pad_pow2(cs);
+    if (cs == 1) return launch_single_member(ref, d_out, num_voxels, s, ev_begin, ev_end, info);
+    if (cs > 16 && !d_todo) return hipErrorInvalidValue;
     int* prep = reinterpret_cast<int*>(d_prep);
-    if (ref.prepare()) launch_kendall_prep(ref, d_members, cs, n_pad, prep, s);
+    if (ref.prepare()) launch_kendall_prep(ref, d_members, cs, pad_pow2(cs), prep, s);
     if (!ref.run()) return hipGetLastError();
-    if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    switch (n_pad) {
-        case 8: launch_kendall_n<8, 4>(d_members, prep, d_out, num_voxels, cs, s); break;
-        case 16: launch_kendall_n<16, 4>(d_members, prep, d_out, num_voxels, cs, s); break;
-        case 32:
-            // measured at 256^3: cs = 32: split 0.55 ms vs monolithic 0.63-1.23 ms; cs = 24: 0.46 vs 1.0-2.4 ms;
-            // cs = 20: 0.41 vs 1.0-2.6 ms.  CRF_RANK_SPLIT32=0 selects the monolithic kernel.
-            if (d_todo && cs > 16 && env_int("CRF_RANK_SPLIT32", 1) != 0) {
-                (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-                const unsigned blocks = unsigned((num_voxels + 63) / 64);
-                if (cs <= 24)
-                    hipLaunchKernelGGL((kendall_split_kernel<16, false, 4, 8, 32>), dim3(blocks), dim3(64), 0, s, d_members,
-                                       prep, d_out, num_voxels, cs, d_todo);
-                else
-                    hipLaunchKernelGGL((kendall_split_kernel<16, false, 4, 16, 32>), dim3(blocks), dim3(64), 0, s,
-                                       d_members, prep, d_out, num_voxels, cs, d_todo);
-                launch_kendall_n<32, 4>(d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                split = true;
-                break;
-            }
-            switch (env_int("CRF_RANK_WAVES32", 4)) {
-                case 2: launch_kendall_n<32, 2>(d_members, prep, d_out, num_voxels, cs, s); break;
-                case 3: launch_kendall_n<32, 3>(d_members, prep, d_out, num_voxels, cs, s); break;
-                default: launch_kendall_n<32, 4>(d_members, prep, d_out, num_voxels, cs, s); break;
-            }
-            break;
-        case 64:
-            // measured at 256^3: cs = 64: split (guarded) 1.49 ms vs monolithic 2.64 ms; cs = 48: 1.24 vs 4.22 ms;
-            // cs = 40: 1.05 vs 4.12 ms.  CRF_RANK_SPLIT64=0 selects the monolithic kernel.
-            if (d_todo && cs > 32 && env_split64_default_on()) {
-                (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-                const bool exact = env_exact() && getenv("CRF_RANK_EXACT");
-                if (cs <= 40)
-                    launch_kendall_split<32, 8, 4>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 48)
-                    launch_kendall_split<32, 16, 4>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 56)
-                    launch_kendall_split<32, 24, 4>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else
-                    launch_kendall_split<32, 32, 4>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                launch_kendall_n<64, 1>(d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                split = true;
-                break;
-            }
-            switch (env_waves(1)) {
-                case 3: launch_kendall_n<64, 3>(d_members, prep, d_out, num_voxels, cs, s); break;
-                case 2: launch_kendall_n<64, 2>(d_members, prep, d_out, num_voxels, cs, s); break;
-                default: launch_kendall_n<64, 1>(d_members, prep, d_out, num_voxels, cs, s); break;
-            }
-            break;
-        default:
-            if (d_todo && env_waves(2) != 0) {
-                (void)hipMemsetAsync(d_todo, 0, sizeof(uint32_t), s);
-                // the guarded instantiation compiles to 226 VGPRs without scratch and is the fastest for every cs
-                // (4.8 ms at 256^3 x 128 vs 12.8 ms unguarded, 13.9-27.7 ms monolithic)
-                const bool exact = env_exact() && getenv("CRF_RANK_EXACT");
-                if (cs <= 72)
-                    launch_kendall_split<64, 8, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 80)
-                    launch_kendall_split<64, 16, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 88)
-                    launch_kendall_split<64, 24, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 96)
-                    launch_kendall_split<64, 32, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 104)
-                    launch_kendall_split<64, 40, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 112)
-                    launch_kendall_split<64, 48, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else if (cs <= 120)
-                    launch_kendall_split<64, 56, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                else
-                    launch_kendall_split<64, 64, 2>(exact, d_members, prep, d_out, num_voxels, cs, s, d_todo);
-                launch_kendall_n<128, 1>(d_members, prep, d_out, num_voxels, cs, s, d_todo);  // voxels with ties
-                split = true;
-            } else {
-                launch_kendall_n<128, 1>(d_members, prep, d_out, num_voxels, cs, s);
-            }
-            break;
-    }
-    if (ev_end) (void)hipEventRecord(ev_end, s);
-    if (info) info->kernel_name = split ? "kendall_split_kernel" : "kendall_kernel";
-    return hipGetLastError();
+    return launch_plan<int>(kendall_plan(cs), d_members, prep, d_out, num_voxels, cs, d_todo, s, ev_begin, ev_end, info);
 }
 
 }  // namespace crf

@@ -35,6 +35,37 @@ def test_rank_member_counts(engine, oracle, measure, omeasure, cs):
     _check(engine, oracle, ens, (5, 6, 4), measure, omeasure, f"{measure.name} cs={cs}")
 
 
+DISPATCH_COUNTS = [2, 8, 9, 16, 17, 24, 25, 31, 32, 33, 40, 41, 48, 49, 56, 57, 63, 64, 65, 72, 73, 80, 81, 88, 89, 96, 97,
+                   104, 105, 112, 113, 120, 121, 127, 128]
+
+
+def _default_kernel(measure, cs):
+    if measure == Measure.KENDALL:
+        return "kendall_kernel" if cs <= 16 else "kendall_split_kernel"
+    if cs <= 16 or cs == 32:
+        return "spearman_kernel"
+    return "spearman_split_kernel" if cs < 32 else "spearman_u32_kernel"
+
+
+DISPATCH_CASES = [(m, o, cs, None) for m, o in MEASURES for cs in DISPATCH_COUNTS]
+DISPATCH_CASES.append((Measure.SPEARMAN, oracle_lib.SPEARMAN, 32, "0"))   # CRF_RANK_U32=0 changes nothing at 32 members
+
+
+@pytest.mark.parametrize("measure,omeasure,cs,u32", DISPATCH_CASES,
+                         ids=[f"{m.name}-{cs}" + ("" if u32 is None else f"-u32={u32}") for m, _, cs, u32 in DISPATCH_CASES])
+def test_rank_default_dispatch(engine, oracle, monkeypatch, measure, omeasure, cs, u32):
+    """No switch set: both sides of every chunk boundary of the dispatch (chunk B = cs - chunk A rounded up to 8).  A
+    grid that is not a multiple of 64 voxels; the box ensemble's plateaus are voxels of exact ties, so the list pass
+    runs as well.  The kernel that answered is the one DESIGN.md's dispatch tables name."""
+    for name in ("CRF_RANK_U32", "CRF_RANK_PAIR"):
+        monkeypatch.delenv(name, raising=False)
+    if u32 is not None:
+        monkeypatch.setenv("CRF_RANK_U32", u32)
+    ens = synth.box_ensemble(20, 12, 9, cs, seed=cs)
+    _check(engine, oracle, ens, (5, 6, 4), measure, omeasure, f"{measure.name} default dispatch cs={cs} u32={u32}")
+    assert engine.last_kernel_name() == _default_kernel(measure, cs)
+
+
 @pytest.mark.parametrize("measure,omeasure", MEASURES)
 def test_rank_ties_everywhere(engine, oracle, measure, omeasure):
     """Heavily tied data (values rounded to a few levels): fractional ranks, tau-b tie terms, x-tie groups, the
