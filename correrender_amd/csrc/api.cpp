@@ -285,22 +285,52 @@ int install_secondary_table(crf_context* c) {
     return CRF_OK;
 }
 
+// Scratch that the per-voxel kernels write (crf_context.h: crf_scratch).  Both functions size every set that the
+// evaluation being issued uses: set 0 alone, or both sets under the range pipeline of compute_to_host, whose ranges run on
+// two streams and may not share a list or a workspace slice.  The pipeline issues its reference-side preparation through
+// the same dispatch as its ranges, with pipeline_voxels = its largest range, before the first range is launched: that
+// call sizes everything, and the calls for the ranges find it large enough (no growth, no synchronisation, between ranges).
+void free_scratch(crf_context* c) {
+    for (crf_scratch& sc : c->scratch) {
+        if (sc.todo) (void)hipFree(sc.todo);
+        if (sc.workspace) (void)hipFree(sc.workspace);
+        sc = crf_scratch{};
+    }
+}
+
+// the most voxels one launch of the evaluation being issued covers: what its blockIdx-indexed workspace is sized for
+size_t launch_voxels(const crf_context* c) { return c->pipeline_voxels ? c->pipeline_voxels : c->num_voxels; }
+
 int ensure_workspace(crf_context* c, size_t need) {
-    if (need > c->workspace_bytes) {
+    for (int set = 0; set < c->pipeline_sets; set++) {
+        crf_scratch& sc = c->scratch[set];
+        if (need <= sc.workspace_bytes) continue;
         CRF_HIP(c, hipDeviceSynchronize());  // an earlier evaluation on a caller stream may still use the old workspace
-        if (c->d_workspace) (void)hipFree(c->d_workspace);
-        c->d_workspace = nullptr;
-        c->workspace_bytes = 0;
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_workspace), need));
-        c->workspace_bytes = need;
+        if (sc.workspace) (void)hipFree(sc.workspace);
+        sc.workspace = nullptr;
+        sc.workspace_bytes = 0;
+        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&sc.workspace), need));
+        sc.workspace_bytes = need;
     }
     return CRF_OK;
 }
 
-// Lazy scratch of the whole local grid.  num_voxels == alloc_voxels whenever no NarrowScope is active (crf_set_grid sets
-// both, nothing else writes them), so every size is taken from alloc_voxels.
-int ensure_todo(crf_context* c) {  // the sort-based rank kernels' list of deferred voxels
-    if (!c->d_todo) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_todo), (c->alloc_voxels + 1) * sizeof(uint32_t)));
+// The sort-based rank kernels' list of deferred voxels.  Set 0 serves the device entry points as well: the whole local
+// grid (num_voxels == alloc_voxels whenever no NarrowScope is active).  Set 1 only ever holds one range.
+int ensure_todo(crf_context* c) {
+    for (int set = 0; set < c->pipeline_sets; set++) {
+        crf_scratch& sc = c->scratch[set];
+        const size_t need = set == 0 ? c->alloc_voxels : c->pipeline_voxels;
+        if (need <= sc.todo_voxels) continue;
+        if (sc.todo) {  // another range layout than the one it was sized for
+            CRF_HIP(c, hipDeviceSynchronize());
+            (void)hipFree(sc.todo);
+        }
+        sc.todo = nullptr;
+        sc.todo_voxels = 0;
+        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&sc.todo), (need + 1) * sizeof(uint32_t)));
+        sc.todo_voxels = need;
+    }
     return CRF_OK;
 }
 
@@ -348,11 +378,13 @@ struct NarrowScope {
         c->num_voxels = std::min(kWindowVoxels, c->alloc_voxels - size_t(w) * kWindowVoxels);
         return size_t(w) * kWindowVoxels;
     }
-    void select_range(int j) {  // range j of ensure_host_ranges
+    void select_range(int j, int scratch_set) {  // range j of ensure_host_ranges, writing the scratch of its stream
         c->d_member_table = c->d_chunk_tables + size_t(j) * size_t(c->cs);
         c->num_voxels = c->chunk_first[j + 1] - c->chunk_first[j];
+        c->scratch_set = scratch_set;
     }
     ~NarrowScope() {
+        c->scratch_set = 0;
         c->d_member_table = table;
         c->d_sec_table = sec_table;
         c->num_voxels = voxels;
@@ -397,8 +429,8 @@ int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream
         if (e == hipErrorNotSupported) {
             if (int r = ensure_workspace(c, crf::direct_symmetric_workspace_bytes(c->cs, c->num_voxels, p->measure))) return r;
             e = crf::launch_direct_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->measure, p->num_bins,
-                                             p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables, c->d_workspace,
-                                             out, s);
+                                             p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables,
+                                             c->scratch[0].workspace, out, s);
             kernel = "direct_symmetric_kernel";
         }
     }
@@ -407,7 +439,7 @@ int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream
         const crf::PairArgs a{p->measure, p->num_bins, p->k, 0, 1, p->min_ref, p->max_ref, p->min_query, p->max_query,
                               kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
         e = crf::launch_pair_requests(c->d_member_table, c->d_sec_table, c->cs, c->xs, c->ys, c->num_voxels, nullptr,
-                                      c->num_voxels, a, c->d_tables, c->d_workspace, out, s);
+                                      c->num_voxels, a, c->d_tables, c->scratch[0].workspace, out, s);
         kernel = "pair_request_kernel";
     }
     if (launch.e0 && launch.e1) (void)hipEventRecord(launch.e1, s);
@@ -575,6 +607,7 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
     const int est = p->kraskov_estimator_index == 2 ? 2 : 1;  // clamp as CorrelationCalculator.cpp:765
     const crf::BinnedArgs ba{p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query,
                              p->measure == CRF_BINNED_MI_CC};
+    const crf_scratch& scratch = c->scratch[c->scratch_set];  // filled in by ensure_todo / ensure_workspace below
     hipError_t e = hipErrorNotSupported;
     if (p->measure != CRF_PEARSON && c->cs > crf::kMaxSortMembers) {
         // any-member-count path: a specialised kernel where one applies, else kernels_generic.hip
@@ -587,14 +620,14 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
                                               e0, e1, info);
         }
         if (e == hipErrorNotSupported) {  // the O(cs^2) counting / repeated-minimum kernels
-            if (int r = ensure_workspace(c, crf::generic_workspace_bytes(c->cs, c->num_voxels))) return r;
+            if (int r = ensure_workspace(c, crf::generic_workspace_bytes(c->cs, launch_voxels(c)))) return r;
             const crf::GenericArgs ga{p->measure, p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, p->k,
                                       est, kraskov_c_term(p->k > 0 ? p->k : 1, est)};
             const bool rank_measure = p->measure == CRF_SPEARMAN || p->measure == CRF_KENDALL;
             if (rank_measure && c->cs <= 256)
                 if (int r = ensure_todo(c)) return r;
-            e = crf::launch_generic(c->d_member_table, c->cs, c->num_voxels, ref, ga, c->d_tables, prep, c->d_workspace,
-                                    out, s, e0, e1, info, rank_measure ? c->d_todo : nullptr);
+            e = crf::launch_generic(c->d_member_table, c->cs, c->num_voxels, ref, ga, c->d_tables, prep, scratch.workspace,
+                                    out, s, e0, e1, info, rank_measure ? scratch.todo : nullptr);
         }
         return launch.finish(e);
     }
@@ -613,7 +646,7 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
             if (c->cs > 16)
                 if (int r = ensure_todo(c)) return r;
             e = (p->measure == CRF_SPEARMAN ? crf::launch_spearman : crf::launch_kendall)(
-                c->d_member_table, c->cs, c->num_voxels, ref, prep, c->d_todo, out, s, e0, e1, info);
+                c->d_member_table, c->cs, c->num_voxels, ref, prep, scratch.todo, out, s, e0, e1, info);
             break;
         case CRF_MI_BINNED:
         case CRF_BINNED_MI_CC:
@@ -809,8 +842,7 @@ void crf_destroy(crf_context* c) {
     if (c->d_prep_slots) (void)hipFree(c->d_prep_slots);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_tables) (void)hipFree(c->d_tables);
-    if (c->d_todo) (void)hipFree(c->d_todo);
-    if (c->d_workspace) (void)hipFree(c->d_workspace);
+    free_scratch(c);
     if (c->d_requests) (void)hipFree(c->d_requests);
     if (c->d_request_out) (void)hipFree(c->d_request_out);
     if (c->d_minmax) (void)hipFree(c->d_minmax);
@@ -849,17 +881,13 @@ int crf_set_grid(crf_context* c, int xs, int ys, int zs, int cs) {
     if (c->d_ref) (void)hipFree(c->d_ref);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_tables) (void)hipFree(c->d_tables);
-    if (c->d_todo) (void)hipFree(c->d_todo);
-    if (c->d_workspace) (void)hipFree(c->d_workspace);
+    free_scratch(c);
     if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
     if (c->h_staging) (void)hipHostFree(c->h_staging);
     c->h_staging = nullptr;
     c->d_staging = nullptr;
     c->d_chunk_tables = nullptr;
     c->host_chunks = 0;
-    c->d_todo = nullptr;
-    c->d_workspace = nullptr;
-    c->workspace_bytes = 0;
     c->d_tables = nullptr;
     c->d_member_table = nullptr;
     c->d_ref = nullptr;
@@ -1183,7 +1211,23 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
         return rc;
     };
 
-    // 1. reference-side tables, once
+    // 1. reference-side tables, once.  The call goes through the dispatch the ranges go through, so it also sizes the
+    //    scratch they write, for the largest range and one set per stream (ensure_todo): ranges in flight together are
+    //    on different streams, so they write different lists, counters and workspace slices.
+    struct PipelineScratch {
+        crf_context* c;
+        PipelineScratch(crf_context* ctx, int sets, size_t voxels) : c(ctx) {
+            c->pipeline_sets = sets;
+            c->pipeline_voxels = voxels;
+        }
+        ~PipelineScratch() {
+            c->pipeline_sets = 1;
+            c->pipeline_voxels = 0;
+        }
+    };
+    size_t largest = 0;
+    for (int j = 0; j < ranges; j++) largest = std::max(largest, c->chunk_first[j + 1] - c->chunk_first[j]);
+    const PipelineScratch sized(c, two_streams ? 2 : 1, largest);
     if (int r = compute_impl(c, p, device_reference_values, nullptr, nullptr, 1u, -1, ov)) return abort_copy(r);
     const double t_prep = trace ? since() : 0.0;
     if (two_streams) {
@@ -1196,8 +1240,9 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
     {
         NarrowScope scope(c);
         for (int j = 0; j < ranges; j++) {
-            scope.select_range(j);
-            hipStream_t s = (two_streams && !(j & 1)) ? c->stream2 : c->stream;  // range 0 on the second stream
+            const bool second = two_streams && !(j & 1);  // range 0 on the second stream
+            scope.select_range(j, second ? 1 : 0);
+            hipStream_t s = second ? c->stream2 : c->stream;
             float* out = out_base + c->chunk_first[j];
             if (int r = compute_impl(c, p, nullptr, out, s, 2u, -1)) return abort_copy(r);
             if (p->flags & CRF_FLAG_ABSOLUTE_VALUE)
@@ -1320,7 +1365,7 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
     if (e == hipErrorNotSupported) {
         e = crf::launch_pair_requests(c->d_member_table, members_j, c->cs, c->xs, c->ys, c->num_voxels,
                                       static_cast<const uint32_t*>(device_requests), num_requests, a, c->d_tables,
-                                      c->d_workspace, static_cast<float*>(device_out), s);
+                                      c->scratch[0].workspace, static_cast<float*>(device_out), s);
         c->last_kernel = "pair_request_kernel";
     }
     return launch_status(c, e);
@@ -1407,7 +1452,7 @@ int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, v
     const double knn_const =
         estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 ? psi_int(c->cs) - psi_int(k) + std::log(2.0) : 0.0;
     return run_windowed(c, device_out, stream, [&](float* o, hipStream_t s, TimedLaunch& t) {
-        return crf::launch_dkl(c->d_member_table, c->cs, c->num_voxels, estimator, num_bins, k, knn_const, c->d_workspace, o,
+        return crf::launch_dkl(c->d_member_table, c->cs, c->num_voxels, estimator, num_bins, k, knn_const, c->scratch[0].workspace, o,
                                s, t.e0, t.e1, &t.info);
     });
 }

@@ -15,6 +15,14 @@
 
 constexpr int kMaxHostChunks = 16;  // z-chunks of a host-output evaluation (kernel of chunk i+1 under the D2H of chunk i)
 
+// Scratch that the per-voxel kernels WRITE.  Launches that share a set must be ordered on one stream.
+struct crf_scratch {
+    uint32_t* todo = nullptr;  // deferred-voxel list of the split-sort rank kernels: a counter, then todo_voxels indices
+    size_t todo_voxels = 0;
+    unsigned char* workspace = nullptr;  // blockIdx-indexed voxel tiles / rank columns of the generic (cs > 128) kernels
+    size_t workspace_bytes = 0;
+};
+
 struct crf_context {
     int device = -1;
     hipStream_t stream = nullptr;  // the context's own stream (used when the caller passes none)
@@ -39,9 +47,12 @@ struct crf_context {
     float* d_prep_slots = nullptr;  // CRF_PREPARED_SLOTS x crf::kPrepBytes, lazily (crf_prepare_device)
     float* d_out = nullptr;    // num_voxels floats, lazily (crf_compute only)
     double* d_tables = nullptr;  // psi / p ln p / noise tables for this member count (crf_internal.h)
-    uint32_t* d_todo = nullptr;  // deferred-voxel list of the split-sort rank kernels, lazily (num_voxels + 1)
-    unsigned char* d_workspace = nullptr;  // voxel tiles of the generic (cs > 128) kernels, lazily
-    size_t workspace_bytes = 0;
+    // [0]: every launch on the context's stream or a caller's; [1]: the ranges of a host-output evaluation that run on
+    // stream2.  Lazily; sized before the first launch of an evaluation, never between its ranges (api.cpp: ensure_todo).
+    crf_scratch scratch[2];
+    int scratch_set = 0;         // the set the launch being issued uses (api.cpp: NarrowScope::select_range)
+    int pipeline_sets = 1;       // while crf_compute runs its range pipeline: the streams it uses, and the voxels of
+    size_t pipeline_voxels = 0;  //   its largest range (0: no pipeline, scratch is sized for num_voxels)
     uint32_t* d_requests = nullptr;  // staging of host pair requests / their results, lazily
     float* d_request_out = nullptr;
     size_t request_capacity = 0;

@@ -21,6 +21,10 @@
  *     context may be in flight at a time unless consecutive calls are ordered on the same stream (or by events).  The
  *     only state meant for overlap across streams are the prepared slots of crf_prepare_device.  crf_set_grid and any
  *     call that has to grow a scratch buffer synchronise the device first.
+ *   - crf_compute (host output) of a result of 8 MiB or more evaluates the grid in voxel ranges on TWO streams of the
+ *     context, so the scratch that the per-voxel kernels write (deferred-voxel list with its counter, workspace) exists
+ *     once per stream there: ranges in flight together never share it, ranges on one stream are ordered.  Both sets are
+ *     sized for the largest range before the first range is launched; nothing is grown between ranges.
  *   - volumes are fp32, x fastest: voxel (x,y,z) at z*xs*ys + y*xs + x  (IDXS, src/Loaders/DataSet.hpp:37);
  *     the ensemble is member-major SoA: one contiguous volume per member
  *     (std::vector<const float*> fields, CorrelationCalculator.cpp:791-800).

@@ -55,3 +55,30 @@ def test_generic_mi_measures(engine, oracle, cs):
         assert_close(got, want, f"generic KSG-{est} cs={cs} k={k}")
     got = engine.compute(Measure.KMI_CORRELATION_COEFFICIENT, reference_values=ref_values, k=k)
     assert_close(got, oracle.field(oracle_lib.KMI_CC, ens, ref_values, k=k), f"generic KMI-CC cs={cs}")
+
+
+@pytest.mark.parametrize("cs,k", [(160, 129), (161, 129), (300, 140)])
+def test_generic_mi_tile_in_the_workspace(engine, oracle, cs, k):
+    """generic_kernel with its voxel tile in the global workspace (tile_bytes(cs) > 60 KiB: from 161 members; 160 is the
+    LDS-tile twin on the other side of the limit).  The MI measures reach it only when the specialised kernels decline:
+    the histogram kernel from 150 bins, the tile-free Kraskov kernel when min(k, cs - 1) > 128."""
+    ens = _data(cs, 900 + cs)
+    _, zs, ys, xs = ens.shape
+    engine.set_grid(xs, ys, zs, cs)
+    engine.upload_members(ens)
+    ref_values = ens[:, 2, 5, 6].copy()
+    finite = ens[np.isfinite(ens)]
+    mm = (float(finite.min()), float(finite.max()))
+    for bins in (150, 255):
+        for m, om in ((Measure.MUTUAL_INFORMATION_BINNED, oracle_lib.MI_BINNED),
+                      (Measure.BINNED_MI_CORRELATION_COEFFICIENT, oracle_lib.BINNED_MI_CC)):
+            got = engine.compute(m, reference_values=ref_values, num_bins=bins, minmax_ref=mm, minmax_query=mm)
+            assert engine.last_kernel_name() == "generic_kernel"
+            assert_close(got, oracle.field(om, ens, ref_values, num_bins=bins, minmax_ref=mm),
+                         f"generic {m.name} cs={cs} bins={bins}")
+    for est in (1, 2):
+        got = engine.compute(Measure.MUTUAL_INFORMATION_KRASKOV, reference_values=ref_values, k=k,
+                             kraskov_estimator_index=est)
+        assert engine.last_kernel_name() == "generic_kernel"
+        assert_close(got, oracle.field(oracle_lib.MI_KRASKOV, ens, ref_values, k=k, estimator=est),
+                     f"generic KSG-{est} cs={cs} k={k}")

@@ -69,8 +69,9 @@ def test_group_matches_the_oracle_and_the_other_reference_sources(engine, oracle
 
 
 def test_group_ranged_host_output_at_a_size_that_is_chunked(engine):
-    """> 8 MB of output: the host-output path evaluates the slab range by range with overlapped copies."""
-    xs, ys, zs, cs = 256, 128, 80, 8
+    """> 8 MB of output: the host-output path evaluates the slab range by range with overlapped copies (the whole grid on
+    the single context, and each of the group's two slabs of 256 x 128 x 68 = 2^21 + 2^17 voxels)."""
+    xs, ys, zs, cs = 256, 128, 136, 8
     rng = np.random.default_rng(3)
     ens = rng.standard_normal((cs, zs, ys, xs), dtype=np.float32)
     engine.set_grid(xs, ys, zs, cs)
