@@ -55,6 +55,10 @@ SYMBOLS = {
     "crf_set_grid": (C.c_int, [_VOIDP, C.c_int, C.c_int, C.c_int, C.c_int]),
     "crf_upload_members": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),
     "crf_bind_members_device": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),
+    "crf_upload_members_format": (C.c_int, [_VOIDP, C.c_int, C.POINTER(_VOIDP)]),
+    "crf_bind_members_device_format": (C.c_int, [_VOIDP, C.c_int, C.POINTER(_VOIDP)]),
+    "crf_member_format": (C.c_int, [_VOIDP]),
+    "crf_last_member_format": (C.c_int, [_VOIDP]),
     "crf_member_minmax": (C.c_int, [_VOIDP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "crf_member_minmax_divergent": (C.c_int, [_VOIDP, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "crf_upload_secondary_members": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),

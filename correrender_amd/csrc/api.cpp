@@ -67,9 +67,25 @@ void drop_packed(crf_context* c) {
     c->pack_state = 0;
 }
 
+// the fp32 copy of members in a narrow native format (crf_context.h); built again by the next call that needs it
+void drop_wide(crf_context* c) {
+    if (c->format == CRF_MEMBER_F32) return;
+    if (c->wide_block) (void)hipFree(c->wide_block);
+    c->wide_block = nullptr;
+    c->members.clear();
+    c->minmax_valid = false;
+    c->host_chunks = 0;
+    c->windows = 0;
+}
+
 void release_members(crf_context* c) {
+    drop_wide(c);
     if (c->owned_block) (void)hipFree(c->owned_block);
     c->owned_block = nullptr;
+    if (c->narrow_owned_block) (void)hipFree(c->narrow_owned_block);
+    c->narrow_owned_block = nullptr;
+    c->narrow.clear();
+    c->format = CRF_MEMBER_F32;
     c->members.clear();
     c->minmax_valid = false;
     drop_packed(c);
@@ -101,11 +117,63 @@ int install_member_table(crf_context* c) {
     return CRF_OK;
 }
 
+const char* format_name(int format) {
+    return format == CRF_MEMBER_U8 ? "u8" : format == CRF_MEMBER_U16 ? "u16" : format == CRF_MEMBER_F16 ? "f16" : "f32";
+}
+
+int install_narrow_table(crf_context* c) {
+    c->narrow_aligned = true;
+    for (const void* p : c->narrow) c->narrow_aligned = c->narrow_aligned && (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
+    CRF_HIP(c, hipMemcpyAsync(c->d_narrow_table, c->narrow.data(), sizeof(void*) * size_t(c->cs), hipMemcpyHostToDevice,
+                              c->stream));
+    CRF_HIP(c, hipStreamSynchronize(c->stream));
+    c->minmax_valid = false;
+    c->host_chunks = 0;
+    c->windows = 0;
+    drop_packed(c);
+    return CRF_OK;
+}
+
+// Members in a narrow native format: the fp32 copy that every kernel but the native Pearson field reads -- one owned
+// block plus the member table, converted on stream s at the first call that needs it (a Pearson-only user never pays
+// for it).  Dropped with the packed copy (drop_wide).
+int ensure_wide(crf_context* c, hipStream_t s) {
+    if (c->format == CRF_MEMBER_F32 || !c->members.empty()) return CRF_OK;
+    if (int r = bind_device(c)) return r;
+    const size_t stride = (c->alloc_voxels + 63) & ~size_t(63);
+    const size_t bytes = stride * sizeof(float) * size_t(c->cs);
+    if (!c->wide_block && hipMalloc(&c->wide_block, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->wide_block = nullptr;
+        return fail(c, CRF_ERR_DEVICE, fmt("no device memory for the fp32 copy of the %s members (%zu bytes)",
+                                           format_name(c->format), bytes));
+    }
+    CRF_HIP(c, crf::launch_widen_members(c->d_narrow_table, c->format, c->cs, c->alloc_voxels,
+                                         static_cast<float*>(c->wide_block), stride, s));
+    c->members.resize(size_t(c->cs));
+    for (int i = 0; i < c->cs; i++) c->members[size_t(i)] = static_cast<const float*>(c->wide_block) + stride * size_t(i);
+    c->max_vpt = 4;
+    CRF_HIP(c, hipMemcpyAsync(c->d_member_table, c->members.data(), sizeof(float*) * size_t(c->cs), hipMemcpyHostToDevice, s));
+    CRF_HIP(c, hipStreamSynchronize(s));
+    c->minmax_valid = false;
+    c->host_chunks = 0;
+    c->windows = 0;
+    return CRF_OK;
+}
+
+// The Pearson field reads narrow members directly (kernels_pearson.hip: pearson_narrow_kernel) when its dword loads can:
+// every member pointer 4-byte aligned; else the evaluation takes the fp32 copy like every other one.
+bool native_pearson(const crf_context* c, const crf_params* p) {
+    return c->format != CRF_MEMBER_F32 && p->measure == CRF_PEARSON && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 &&
+           c->cs <= crf::kNarrowMaxMembers && c->narrow_aligned && !c->windowed;
+}
+
 // Packs the members for the Pearson field if the layout policy asks for it (include/corrfield.h: crf_member_layout),
 // once per set of members, on stream s.  *use: the packed copy is there for this evaluation.
 int ensure_packed(crf_context* c, hipStream_t s, crf::PackedMembers* use) {
     *use = crf::PackedMembers{};
     const int cs = c->cs;
+    if (c->format != CRF_MEMBER_F32) return CRF_OK;  // the packed copy is an fp32 format
     if (c->member_layout == CRF_MEMBER_LAYOUT_RAW || cs < crf::kPackMinMembers || cs > crf::kPackMaxMembers ||
         c->windowed || c->num_voxels != c->alloc_voxels)
         return CRF_OK;
@@ -203,7 +271,8 @@ double kraskov_c_term(int k, int estimator) {
 int check_ready(crf_context* c) {
     if (!c) return CRF_ERR_ARGUMENT;
     if (c->cs <= 0 || c->num_voxels == 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
-    if (int(c->members.size()) != c->cs) return fail(c, CRF_ERR_STATE, "no member volumes uploaded or bound");
+    if (int(c->format == CRF_MEMBER_F32 ? c->members.size() : c->narrow.size()) != c->cs)
+        return fail(c, CRF_ERR_STATE, "no member volumes uploaded or bound");
     return CRF_OK;
 }
 
@@ -367,10 +436,12 @@ struct NarrowScope {
     crf_context* c;
     const float** table;
     const float** sec_table;
+    const void** format_table;
     size_t voxels;
     int vpt;
     explicit NarrowScope(crf_context* ctx)
-        : c(ctx), table(ctx->d_member_table), sec_table(ctx->d_sec_table), voxels(ctx->num_voxels), vpt(ctx->max_vpt) {}
+        : c(ctx), table(ctx->d_member_table), sec_table(ctx->d_sec_table), format_table(ctx->d_narrow_table),
+          voxels(ctx->num_voxels), vpt(ctx->max_vpt) {}
     size_t select_window(int w) {  // returns the window's first voxel
         const size_t per = size_t(c->window_has_secondary ? 2 : 1) * size_t(c->cs);
         c->d_member_table = c->d_window_tables + size_t(w) * per;
@@ -379,7 +450,11 @@ struct NarrowScope {
         return size_t(w) * kWindowVoxels;
     }
     void select_range(int j, int scratch_set) {  // range j of ensure_host_ranges, writing the scratch of its stream
-        c->d_member_table = c->d_chunk_tables + size_t(j) * size_t(c->cs);
+        const float** range_table = c->d_chunk_tables + size_t(j) * size_t(c->cs);
+        if (c->chunk_native)
+            c->d_narrow_table = reinterpret_cast<const void**>(range_table);
+        else
+            c->d_member_table = range_table;
         c->num_voxels = c->chunk_first[j + 1] - c->chunk_first[j];
         c->scratch_set = scratch_set;
     }
@@ -387,6 +462,7 @@ struct NarrowScope {
         c->scratch_set = 0;
         c->d_member_table = table;
         c->d_sec_table = sec_table;
+        c->d_narrow_table = format_table;
         c->num_voxels = voxels;
         c->max_vpt = vpt;
     }
@@ -557,6 +633,12 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
     float* out = static_cast<float*>(device_out);
+    const bool native = native_pearson(c, p);
+    if (ov && c->format != CRF_MEMBER_F32)
+        return fail(c, CRF_ERR_UNSUPPORTED, "a direct reference read needs fp32 members");
+    if (!native)
+        if (int r = ensure_wide(c, s)) return r;
+    if (phase & 2u) c->last_format = native ? c->format : CRF_MEMBER_F32;
     if (symmetric) {
         if (phase != 3u) return fail(c, CRF_ERR_ARGUMENT, "the symmetric mode has no reference-side preparation");
         if (c->sec_members.empty())
@@ -633,6 +715,18 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
     }
     switch (p->measure) {
         case CRF_PEARSON: {
+            if (native) {
+                if ((phase & 1u) && !ref.values) {  // the reference point: its converted values, through d_ref
+                    CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, ref.voxel, c->d_ref, s));
+                    ref.values = c->d_ref;
+                }
+                const uintptr_t vector_bytes = c->format == CRF_MEMBER_U8 ? 16 : 8;  // one lane's results
+                e = crf::launch_pearson_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels,
+                                               reinterpret_cast<uintptr_t>(out) % vector_bytes == 0, ref, prep, out, s, e0,
+                                               e1, info);
+                if (phase & 2u) c->last_layout = CRF_MEMBER_LAYOUT_RAW;
+                break;
+            }
             crf::PackedMembers packed;
             if (phase & 2u)
                 if (int r = ensure_packed(c, s, &packed)) return r;
@@ -677,6 +771,7 @@ int compute_impl(crf_context* c, const crf_params* p, const void* device_referen
                  void* stream, unsigned phase, int slot, const crf::RefOverride* ov = nullptr) {
     if (!c || !c->windowed || !p || (p->flags & CRF_FLAG_SYMMETRIC))
         return compute_impl_one(c, p, device_reference_values, device_out, stream, phase, slot, ov);
+    if (int r = ensure_wide(c, stream_of(c, stream))) return r;  // the window tables point into the fp32 members
     if (phase & 1u)
         if (int r = compute_impl_one(c, p, device_reference_values, nullptr, stream, 1u, slot, ov)) return r;
     if (!(phase & 2u)) return CRF_OK;
@@ -697,8 +792,11 @@ int apply_abs(crf_context* c, const crf_params* p, void* device_out, void* strea
 // first voxel), so that every per-voxel kernel can be launched on a range without knowing about ranges.  Range lengths
 // are multiples of 1024 voxels (4 KiB: every range stays as aligned as the members themselves) and shrink towards the
 // end: the copy of the last range into the caller's buffer is the only host work no kernel hides.
-int ensure_host_ranges(crf_context* c) {
-    if (c->host_chunks > 0) return CRF_OK;
+// native: the tables hold the narrow members' pointers (the native Pearson field), advanced by whole elements; a range
+// starts at a multiple of 1024 voxels, so they stay 4-byte aligned and every range but the last is whole dwords.
+int ensure_host_ranges(crf_context* c, bool native) {
+    if (c->host_chunks > 0 && c->chunk_native == native) return CRF_OK;
+    c->host_chunks = 0;
     const size_t n = c->alloc_voxels;
     std::vector<size_t> first{0};
     const int forced = env_int_or("CRF_HOST_CHUNKS", 0);
@@ -736,8 +834,12 @@ int ensure_host_ranges(crf_context* c) {
     const int ranges = int(first.size());
     first.push_back(n);
     std::vector<const float*> table(size_t(ranges) * size_t(c->cs));
+    const size_t element = crf::member_format_bytes(c->format);
     for (int j = 0; j < ranges; j++)
-        for (int m = 0; m < c->cs; m++) table[size_t(j) * size_t(c->cs) + size_t(m)] = c->members[size_t(m)] + first[size_t(j)];
+        for (int m = 0; m < c->cs; m++)
+            table[size_t(j) * size_t(c->cs) + size_t(m)] =
+                native ? reinterpret_cast<const float*>(static_cast<const char*>(c->narrow[size_t(m)]) + first[size_t(j)] * element)
+                       : c->members[size_t(m)] + first[size_t(j)];
     if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
     c->d_chunk_tables = nullptr;
     CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_chunk_tables), table.size() * sizeof(float*)));
@@ -750,6 +852,7 @@ int ensure_host_ranges(crf_context* c) {
     if (!c->prep_done) CRF_HIP(c, hipEventCreateWithFlags(&c->prep_done, hipEventDisableTiming));
     for (int j = 0; j <= ranges; j++) c->chunk_first[j] = first[size_t(j)];
     c->host_chunks = ranges;
+    c->chunk_native = native;
     return CRF_OK;
 }
 
@@ -759,6 +862,7 @@ template <class Launch>
 int run_windowed(crf_context* c, void* device_out, void* stream, Launch&& launch) {
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
+    if (int r = ensure_wide(c, s)) return r;
     TimedLaunch timed(c);
     hipError_t e = hipSuccess;
     const int rc = for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
@@ -836,6 +940,7 @@ void crf_destroy(crf_context* c) {
     release_members(c);
     release_secondary(c);
     if (c->d_member_table) (void)hipFree(c->d_member_table);
+    if (c->d_narrow_table) (void)hipFree(c->d_narrow_table);
     if (c->d_sec_table) (void)hipFree(c->d_sec_table);
     if (c->d_ref) (void)hipFree(c->d_ref);
     if (c->d_prep) (void)hipFree(c->d_prep);
@@ -876,6 +981,8 @@ int crf_set_grid(crf_context* c, int xs, int ys, int zs, int cs) {
     release_members(c);
     release_secondary(c);
     if (c->d_member_table) (void)hipFree(c->d_member_table);
+    if (c->d_narrow_table) (void)hipFree(c->d_narrow_table);
+    c->d_narrow_table = nullptr;
     if (c->d_sec_table) (void)hipFree(c->d_sec_table);
     c->d_sec_table = nullptr;
     if (c->d_ref) (void)hipFree(c->d_ref);
@@ -907,6 +1014,7 @@ int crf_set_grid(crf_context* c, int xs, int ys, int zs, int cs) {
     c->d_window_tables = nullptr;
     c->windows = 0;
     CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_member_table), sizeof(float*) * size_t(cs)));
+    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_narrow_table), sizeof(void*) * size_t(cs)));
     CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_ref), sizeof(float) * size_t(cs)));
     const std::vector<double> tables = build_tables(cs);
     CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_tables), tables.size() * sizeof(double)));
@@ -972,11 +1080,61 @@ int crf_bind_members_device(crf_context* c, const void* const* device_members) {
     return install_member_table(c);
 }
 
+// the checks the two format calls share; *narrow: a narrow format (else the call is the fp32 call)
+static int check_member_format(crf_context* c, int format, const void* const* members, bool* narrow) {
+    if (!c || !members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (format < CRF_MEMBER_F32 || format > CRF_MEMBER_F16)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("unknown member format %d", format));
+    *narrow = format != CRF_MEMBER_F32;
+    if (!*narrow) return CRF_OK;
+    if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
+    for (int i = 0; i < c->cs; i++)
+        if (!members[i]) return fail(c, CRF_ERR_ARGUMENT, fmt("member %d is a null pointer", i));
+    // the native kernel addresses a member with 32-bit byte offsets (crf_internal.h: kNarrowMaxBytes, just under 4 GiB)
+    if (c->alloc_voxels * crf::member_format_bytes(format) >= crf::kNarrowMaxBytes)
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%s members of 4 GiB or more are not supported (%zu voxels per member)",
+                                                format_name(format), c->alloc_voxels));
+    return bind_device(c);
+}
+
+int crf_upload_members_format(crf_context* c, int format, const void* const* host_members) {
+    bool narrow = false;
+    if (int r = check_member_format(c, format, host_members, &narrow)) return r;
+    if (!narrow) return crf_upload_members(c, reinterpret_cast<const float* const*>(host_members));
+    release_members(c);
+    const size_t bytes = c->num_voxels * crf::member_format_bytes(format);
+    const size_t stride = (bytes + 255) & ~size_t(255);  // every member starts 256-B aligned
+    CRF_HIP(c, hipMalloc(&c->narrow_owned_block, stride * size_t(c->cs)));
+    c->format = format;
+    c->narrow.resize(size_t(c->cs));
+    for (int i = 0; i < c->cs; i++) {
+        char* dst = static_cast<char*>(c->narrow_owned_block) + stride * size_t(i);
+        c->narrow[size_t(i)] = dst;
+        CRF_HIP(c, hipMemcpyAsync(dst, host_members[i], bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return install_narrow_table(c);
+}
+
+int crf_bind_members_device_format(crf_context* c, int format, const void* const* device_members) {
+    bool narrow = false;
+    if (int r = check_member_format(c, format, device_members, &narrow)) return r;
+    if (!narrow) return crf_bind_members_device(c, device_members);
+    release_members(c);
+    c->format = format;
+    c->narrow.assign(device_members, device_members + c->cs);
+    return install_narrow_table(c);
+}
+
+int crf_member_format(const crf_context* c) { return c ? c->format : CRF_MEMBER_F32; }
+
+int crf_last_member_format(const crf_context* c) { return c ? c->last_format : CRF_MEMBER_F32; }
+
 int crf_member_minmax(crf_context* c, float* out_min, float* out_max) {
     if (int r = check_ready(c)) return r;
     if (!out_min || !out_max) return fail(c, CRF_ERR_ARGUMENT, "null output");
     if (!c->minmax_valid) {
         if (int r = bind_device(c)) return r;
+        if (int r = ensure_wide(c, c->stream)) return r;
         CRF_HIP(c, crf::launch_minmax(c->d_member_table, c->cs, c->num_voxels, c->d_minmax, c->stream));
         uint32_t keys[2];
         CRF_HIP(c, hipMemcpyAsync(keys, c->d_minmax, sizeof keys, hipMemcpyDeviceToHost, c->stream));
@@ -1056,6 +1214,7 @@ int crf_gather_reference_device(crf_context* c, int x, int y, int z, void* devic
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
+    if (int r = ensure_wide(c, s)) return r;
     CRF_HIP(c, crf::launch_gather_reference(c->d_member_table, c->cs, voxel, static_cast<float*>(device_out), s));
     return CRF_OK;
 }
@@ -1073,6 +1232,7 @@ int crf_gather_reference_rows_device(crf_context* c, const int32_t* xyz, int num
     }
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
+    if (int r = ensure_wide(c, s)) return r;
     CRF_HIP(c, crf::launch_gather_reference_rows(c->d_member_table, c->cs, rows, num_rows,
                                                  static_cast<float*>(device_rows), s));
     return CRF_OK;
@@ -1096,6 +1256,8 @@ int gather_reference_to(crf_context* c, bool secondary, int x, int y, int z, flo
     size_t voxel;
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
+    if (!secondary)
+        if (int r = ensure_wide(c, s)) return r;
     CRF_HIP(c, launch_gather_reference(secondary ? c->d_sec_table : c->d_member_table, c->cs, voxel, device_out, s));
     return CRF_OK;
 }
@@ -1111,6 +1273,8 @@ int reference_override(crf_context* owner, bool secondary, int x, int y, int z, 
     if (int r = check_ready(owner)) return r;
     if (secondary && owner->sec_members.empty()) return fail(owner, CRF_ERR_STATE, "no secondary members are bound");
     if (int r = ref_voxel(owner, x, y, z, &out->voxel)) return r;
+    if (!secondary && owner->format != CRF_MEMBER_F32)
+        return fail(owner, CRF_ERR_UNSUPPORTED, "a direct reference read needs fp32 members");
     out->table = secondary ? owner->d_sec_table : owner->d_member_table;
     return CRF_OK;
 }
@@ -1145,7 +1309,10 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
         if (int r = compute_device_ex(c, p, device_reference_values, c->d_out, nullptr, ov)) return r;
         return copy_result_to_host(c, c->d_out, host_out, c->alloc_voxels);
     }
-    if (int r = ensure_host_ranges(c)) return r;
+    const bool native = native_pearson(c, p);
+    if (!native)
+        if (int r = ensure_wide(c, c->stream)) return r;  // (the second stream is ordered behind the preparation below)
+    if (int r = ensure_host_ranges(c, native)) return r;
     const int ranges = c->host_chunks;
     // pinned, device-mapped staging for the whole local result
     if (!c->h_staging) {
@@ -1333,6 +1500,7 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
         return fail(c, CRF_ERR_UNSUPPORTED, "pair requests address voxels with 32-bit byte offsets: member volumes of 4 GiB or more are not supported in request mode");
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
+    if (int r = ensure_wide(c, s)) return r;
     if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, num_requests))) return r;
     // two-field request mode: the j side reads the secondary members (CRF_FLAG_QUERY_FROM_SECONDARY)
     const float* const* members_j = c->d_member_table;
@@ -1535,6 +1703,7 @@ int crf_members_changed(crf_context* c) {
     c->host_chunks = 0;
     c->windows = 0;
     drop_packed(c);
+    drop_wide(c);
     return CRF_OK;
 }
 

@@ -35,6 +35,16 @@ struct crf_context {
     std::vector<const float*> members;  // cs device pointers (owned or borrowed)
     const float** d_member_table = nullptr;
     int max_vpt = 1;
+    // primary members in a narrow native format (crf_upload_members_format / crf_bind_members_device_format): `narrow`
+    // holds the cs device pointers and `members` stays empty until a call that needs fp32 members builds the widened
+    // copy (api.cpp: ensure_wide), one owned block; the Pearson field at 2..128 members reads `narrow` directly
+    int format = CRF_MEMBER_F32;
+    void* narrow_owned_block = nullptr;
+    std::vector<const void*> narrow;
+    const void** d_narrow_table = nullptr;
+    bool narrow_aligned = false;       // every narrow pointer is 4-byte aligned (the native kernel loads dwords)
+    void* wide_block = nullptr;        // the widened copy, lazily
+    int last_format = CRF_MEMBER_F32;  // what the per-voxel kernel of the last field evaluation read
     // secondary members (second scalar field of the SEPARATE / SEPARATE_SYMMETRIC modes), optional
     void* sec_owned_block = nullptr;
     std::vector<const float*> sec_members;
@@ -77,6 +87,7 @@ struct crf_context {
     // threads moves finished ranges into the caller's buffer (api.cpp: compute_to_host)
     const float** d_chunk_tables = nullptr;  // host_chunks x cs pointers
     int host_chunks = 0;                     // 0: tables not built for the current members
+    bool chunk_native = false;               // the tables hold the narrow pointers (native Pearson field), not fp32 ones
     size_t chunk_first[kMaxHostChunks + 1] = {};  // first voxel of every range; [host_chunks] = alloc_voxels
     std::atomic<int> chunk_ready[kMaxHostChunks] = {};  // 1: range landed in the staging buffer, -1: evaluation failed
     hipStream_t stream2 = nullptr;           // odd ranges (the next range fills the GPU while the previous one drains)

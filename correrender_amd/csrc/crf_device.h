@@ -57,6 +57,20 @@ __device__ __forceinline__ float load_member(const float* base, uint32_t byte_of
     return *(gptr)((gcptr)base + byte_offset);
 }
 
+// One element of a member in a narrow native format as the value the calculators see (crf_internal.h; reference:
+// HostCacheEntry.cpp:107-176).  `/` is the correctly rounded IEEE quotient (Makefile).
+template <int FMT>
+__device__ __forceinline__ float narrow_value(const void* base, size_t i) {
+    static_assert(FMT == CRF_MEMBER_U8 || FMT == CRF_MEMBER_U16 || FMT == CRF_MEMBER_F16, "a narrow format");
+    if constexpr (FMT == CRF_MEMBER_U8) {
+        return float(static_cast<const uint8_t*>(base)[i]) / 255.0f;
+    } else if constexpr (FMT == CRF_MEMBER_U16) {
+        return float(static_cast<const uint16_t*>(base)[i]) / 65535.0f;
+    } else {
+        return float(static_cast<const _Float16*>(base)[i]);  // half denormals are fp32 normals: exact
+    }
+}
+
 __device__ __forceinline__ float load_ref(const RefSource& r, const float* const* __restrict__ members, int c) {
     if (r.values) return r.values[c];
     return (r.table ? r.table : members)[c][r.voxel];

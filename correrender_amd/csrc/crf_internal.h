@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/corrfield.h"
+
 namespace crf {
 
 // Largest member count the register-resident kernels are instantiated for; above it the streaming
@@ -150,6 +152,30 @@ hipError_t launch_pearson(const float* const* d_members, int cs, size_t num_voxe
 // tiles = ceil(num_voxels / 64), and adds the number of member segments that fall back to *d_fallbacks.
 hipError_t launch_pack_members(const float* const* d_members, int cs, size_t num_voxels, unsigned char* header,
                                unsigned char* body, uint32_t* d_fallbacks, hipStream_t s);
+// ---- narrow primary members (include/corrfield.h: crf_member_format) ---------------------------------------------
+// The value the calculators see of a u8 / u16 / f16 element is float(b) / 255.0f, float(s) / 65535.0f, float(h)
+// (reference: src/Volume/Cache/HostCacheEntry.cpp:107-176).  The Pearson field at 2..kNarrowMaxMembers members reads
+// such members directly (kernels_pearson.hip: pearson_narrow_kernel); everything else runs on an fp32 copy that
+// launch_widen_members builds (kernels_common.hip).
+constexpr int kNarrowMaxMembers = 128;
+// A narrow member must be smaller than this: the native kernel's 32-bit voxel index and byte offset of the last block's
+// surplus lanes (up to 1020 voxels past the end) must not wrap.
+constexpr size_t kNarrowMaxBytes = size_t(0xFFFF0000u);
+inline size_t member_format_bytes(int format) {
+    return format == CRF_MEMBER_U8 ? 1 : format == CRF_MEMBER_F32 ? 4 : 2;
+}
+// d_narrow: cs device pointers to num_voxels elements of `format` each, every one 4-byte aligned; num_voxels x element
+// size below kNarrowMaxBytes.  ref.values holds the cs (converted) reference values when ref.prepare().  out_vector: d_out is
+// aligned for one vector store of a lane's 2 (16-bit) or 4 (8-bit) results.
+hipError_t launch_pearson_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, bool out_vector,
+                                 const RefSource& ref, float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin,
+                                 hipEvent_t ev_end, LaunchInfo* info);
+// member c of the fp32 copy = d_block + c * stride, num_voxels converted values each
+hipError_t launch_widen_members(const void* const* d_narrow, int format, int cs, size_t num_voxels, float* d_block,
+                                size_t stride, hipStream_t s);
+// d_out[c] = converted value of d_narrow[c][voxel]
+hipError_t launch_gather_reference_narrow(const void* const* d_narrow, int format, int cs, size_t voxel, float* d_out,
+                                          hipStream_t s);
 hipError_t launch_fill(float* d_out, size_t n, float value, hipStream_t s);
 hipError_t launch_abs(float* d_out, size_t n, hipStream_t s);  // in place |.| (CRF_FLAG_ABSOLUTE_VALUE on a field)
 

@@ -471,6 +471,12 @@ int group_compute(crf_group* g, const crf_params* params, int count, float* cons
                 if (!device_outs[size_t(i) * size_t(g->n) + size_t(r)])
                     return gfail(g, CRF_ERR_ARGUMENT, fmt("device output of evaluation %d, slot %d is a null pointer", i, r));
     }
+    // the exchange reads another context's member table as fp32 (crf::RefOverride)
+    for (int r = 0; r < g->n; r++)
+        if (g->ctx[size_t(r)]->format != CRF_MEMBER_F32)
+            return gfail(g, CRF_ERR_UNSUPPORTED,
+                         fmt("device groups evaluate fp32 members only: the context of slot %d holds members in a narrow "
+                             "native format (crf_bind_members_device_format)", r));
     std::vector<RefPlan> plans(static_cast<size_t>(count));
     for (int i = 0; i < count; i++)
         if (int rc = plan_reference(g, &params[i], &plans[size_t(i)])) return rc;

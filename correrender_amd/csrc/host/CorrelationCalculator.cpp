@@ -325,16 +325,31 @@ void CorrelationCalculator::ensureMembersResident(int timeStepIdx, int ensembleI
             throwBackendError("calculateCpu");
     }
     std::vector<HostCacheEntry> fieldEntries;
-    std::vector<const float*> fields;
     fieldEntries.reserve(size_t(cs));
-    fields.reserve(size_t(cs));
-    for (int fieldIdx = 0; fieldIdx < cs; fieldIdx++) {
-        HostCacheEntry fieldEntry = getFieldEntryCpu(fieldName, fieldIdx, timeStepIdx, ensembleIdx);
-        fieldEntries.push_back(fieldEntry);
-        fields.push_back(fieldEntry->data<float>());
+    for (int fieldIdx = 0; fieldIdx < cs; fieldIdx++)
+        fieldEntries.push_back(getFieldEntryCpu(fieldName, fieldIdx, timeStepIdx, ensembleIdx));
+    // Members that all share one narrow native format go to a single device as they are stored (crf_member_format:
+    // half or a quarter of the bytes cross the bus and stay resident, and no float view is converted on the host);
+    // a device group, and members of mixed formats, take the float views.
+    const ScalarDataFormat native = fieldEntries[0]->getScalarDataFormatNative();
+    bool sameFormat = true;
+    for (const HostCacheEntry& entry : fieldEntries) sameFormat = sameFormat && entry->getScalarDataFormatNative() == native;
+    int format = CRF_MEMBER_F32;
+    if (!group && sameFormat && native != ScalarDataFormat::FLOAT)
+        format = native == ScalarDataFormat::BYTE ? CRF_MEMBER_U8 : native == ScalarDataFormat::SHORT ? CRF_MEMBER_U16 : CRF_MEMBER_F16;
+    if (format != CRF_MEMBER_F32) {
+        std::vector<const void*> natives;
+        natives.reserve(size_t(cs));
+        for (const HostCacheEntry& entry : fieldEntries) natives.push_back(entry->getDataNative());
+        if (crf_upload_members_format(ctx, format, natives.data())) throwBackendError("calculateCpu");
+    } else {
+        std::vector<const float*> fields;
+        fields.reserve(size_t(cs));
+        for (const HostCacheEntry& entry : fieldEntries) fields.push_back(entry->data<float>());
+        if (group ? crf_group_upload_members(group, fields.data()) : crf_upload_members(ctx, fields.data()))
+            throwBackendError("calculateCpu");
     }
-    if (group ? crf_group_upload_members(group, fields.data()) : crf_upload_members(ctx, fields.data()))
-        throwBackendError("calculateCpu");
+    residentFormat = format;
     residentGeneration = volumeData->getDataGeneration();
     residentField = fieldName;
     residentCs = cs;

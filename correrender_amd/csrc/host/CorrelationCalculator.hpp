@@ -96,6 +96,9 @@ public:
     /// Kernel time of the last calculateCpu in ms (HIP events around the per-voxel kernels; slowest device of a group),
     /// < 0 if unavailable.
     double getLastKernelTimeMs() const { return lastKernelMs; }
+    /// crf_member_format of the members the last calculateCpu left resident on the device: a narrow format when every
+    /// member entry shared it and one device evaluates, else CRF_MEMBER_F32.
+    int getResidentMemberFormat() const { return residentFormat; }
 
 protected:
     void onCorrelationMemberCountChanged() override;
@@ -116,6 +119,7 @@ private:
     std::string residentField;
     int residentT = -1, residentE = -1, residentCs = -1;
     bool residentEnsembleMode = true;
+    int residentFormat = CRF_MEMBER_F32;
     int cachedMemberCount = 0;
     CorrelationMeasureType correlationMeasureType = CorrelationMeasureType::MUTUAL_INFORMATION_KRASKOV;
     bool useGpu = true;   ///< "device" setting: "CPU" is accepted and remembered, evaluation always runs on the GPU.

@@ -7,6 +7,103 @@
 
 namespace crfhost {
 
+float halfToFloat(uint16_t h) {
+    const uint32_t sign = uint32_t(h & 0x8000u) << 16, exponent = (h >> 10) & 31u, mantissa = h & 0x3FFu;
+    uint32_t bits;
+    if (exponent == 0) {  // zero or denormal: mantissa * 2^-24, exact in float
+        const float magnitude = float(mantissa) * 5.9604644775390625e-8f;
+        std::memcpy(&bits, &magnitude, sizeof bits);
+        bits |= sign;
+    } else if (exponent == 31) {
+        bits = sign | 0x7F800000u | (mantissa << 13);
+    } else {
+        bits = sign | ((exponent + 112u) << 23) | (mantissa << 13);
+    }
+    float f;
+    std::memcpy(&f, &bits, sizeof f);
+    return f;
+}
+
+uint16_t floatToHalf(float f) {
+    uint32_t bits;
+    std::memcpy(&bits, &f, sizeof bits);
+    const uint16_t sign = uint16_t((bits >> 16) & 0x8000u);
+    const uint32_t magnitude = bits & 0x7FFFFFFFu;
+    if (magnitude > 0x7F800000u) return uint16_t(sign | 0x7E00u | ((magnitude >> 13) & 0x3FFu));  // NaN stays NaN
+    if (magnitude >= 0x47800000u) return uint16_t(sign | 0x7C00u);                                // 65536 and above
+    uint32_t kept, rest, half;
+    if (magnitude >= 0x38800000u) {  // a half normal (2^-14 and above): rebias, drop 13 bits
+        const uint32_t v = magnitude - (112u << 23);
+        kept = v >> 13;
+        rest = v & 0x1FFFu;
+        half = 0x1000u;
+    } else {  // a half denormal: multiples of 2^-24
+        const uint32_t exponent = magnitude >> 23;
+        if (exponent < 102u) return sign;  // below 2^-25: zero
+        const uint32_t shift = 126u - exponent;  // 14..24
+        const uint32_t m = (magnitude & 0x7FFFFFu) | 0x800000u;
+        kept = m >> shift;
+        rest = m & ((1u << shift) - 1u);
+        half = 1u << (shift - 1u);
+    }
+    if (rest > half || (rest == half && (kept & 1u))) kept++;  // to nearest even; a carry moves up one binade (or to inf)
+    return uint16_t(sign | kept);
+}
+
+HostCacheEntryType::HostCacheEntryType(size_t numEntries, ScalarDataFormat format, uint16_t* dataOwned)
+    : numEntries(numEntries), scalarDataFormatNative(format) {
+    if (format == ScalarDataFormat::SHORT) {
+        dataShort = dataOwned;
+    } else if (format == ScalarDataFormat::FLOAT16) {
+        dataFloat16 = dataOwned;
+    } else {
+        delete[] dataOwned;
+        throw CalculatorError("Error in HostCacheEntryType: 16-bit data is SHORT or FLOAT16.");
+    }
+}
+
+HostCacheEntryType::~HostCacheEntryType() {
+    delete[] dataFloat;
+    delete[] dataByte;
+    delete[] dataShort;
+    delete[] dataFloat16;
+}
+
+const void* HostCacheEntryType::getDataNative() const {
+    switch (scalarDataFormatNative) {
+        case ScalarDataFormat::BYTE: return dataByte;
+        case ScalarDataFormat::SHORT: return dataShort;
+        case ScalarDataFormat::FLOAT16: return dataFloat16;
+        default: return dataFloat;
+    }
+}
+
+const float* HostCacheEntryType::getDataFloat() const {
+    if (!dataFloat) {
+        auto* converted = new float[numEntries];
+        for (size_t i = 0; i < numEntries; i++) converted[i] = getDataFloatAt(i);
+        dataFloat = converted;
+    }
+    return dataFloat;
+}
+
+float HostCacheEntryType::getDataFloatAt(size_t idx) const {
+    if (dataFloat) return dataFloat[idx];
+    if (scalarDataFormatNative == ScalarDataFormat::BYTE) return float(dataByte[idx]) / 255.0f;
+    if (scalarDataFormatNative == ScalarDataFormat::SHORT) return float(dataShort[idx]) / 65535.0f;
+    if (scalarDataFormatNative == ScalarDataFormat::FLOAT16) return halfToFloat(dataFloat16[idx]);
+    return 0.0f;
+}
+
+void HostCacheEntryType::switchNativeFormat(ScalarDataFormat newNativeFormat) {
+    if (scalarDataFormatNative != ScalarDataFormat::FLOAT || newNativeFormat != ScalarDataFormat::FLOAT16)
+        throw CalculatorError("Error in HostCacheEntryType::switchNativeFormat: "
+                              "Currently, only switching from float to float16 is supported.");
+    scalarDataFormatNative = newNativeFormat;
+    dataFloat16 = new uint16_t[numEntries];
+    for (size_t i = 0; i < numEntries; i++) dataFloat16[i] = floatToHalf(dataFloat[i]);
+}
+
 void VolumeData::setGridExtent(float dx, float dy, float dz) {
     box.min = {0.0f, 0.0f, 0.0f};
     box.max = {float(xs - 1) * dx, float(ys - 1) * dy, float(zs - 1) * dz};
@@ -23,6 +120,27 @@ void VolumeData::setFieldData(const std::string& fieldName, int timeStepIdx, int
     auto* copy = new float[n];
     std::memcpy(copy, values, n * sizeof(float));
     storage[Access(fieldName, timeStepIdx, ensembleIdx)] = std::make_shared<HostCacheEntryType>(n, copy);
+    if (std::find(fieldNames.begin(), fieldNames.end(), fieldName) == fieldNames.end()) fieldNames.push_back(fieldName);
+    fieldMinMaxCache.clear();
+    hostFieldCache.clear();
+    dataGeneration++;
+}
+
+void VolumeData::setFieldData(const std::string& fieldName, int timeStepIdx, int ensembleIdx, ScalarDataFormat format,
+                              const void* values) {
+    if (format == ScalarDataFormat::FLOAT) return setFieldData(fieldName, timeStepIdx, ensembleIdx, static_cast<const float*>(values));
+    const size_t n = getSlice3dEntryCount();
+    HostCacheEntry entry;
+    if (format == ScalarDataFormat::BYTE) {
+        auto* copy = new uint8_t[n];
+        std::memcpy(copy, values, n);
+        entry = std::make_shared<HostCacheEntryType>(n, copy);
+    } else {
+        auto* copy = new uint16_t[n];
+        std::memcpy(copy, values, n * sizeof(uint16_t));
+        entry = std::make_shared<HostCacheEntryType>(n, format, copy);
+    }
+    storage[Access(fieldName, timeStepIdx, ensembleIdx)] = entry;
     if (std::find(fieldNames.begin(), fieldNames.end(), fieldName) == fieldNames.end()) fieldNames.push_back(fieldName);
     fieldMinMaxCache.clear();
     hostFieldCache.clear();

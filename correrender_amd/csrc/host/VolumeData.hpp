@@ -15,6 +15,8 @@
 // No loaders, no device caches, no rendering: inputs are handed in as arrays.
 #pragma once
 #include <array>
+#include <cstddef>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <string>
@@ -25,21 +27,47 @@
 
 namespace crfhost {
 
+/// Native storage format of a scalar field (the reference's ScalarDataFormat, src/Volume/Cache/HostCacheEntry.hpp).
+enum class ScalarDataFormat { FLOAT, BYTE, SHORT, FLOAT16 };
+
+/// IEEE binary16 <-> binary32 on the bit patterns: halfToFloat is exact (half denormals are float normals),
+/// floatToHalf rounds to nearest even, overflows to infinity and keeps NaN a NaN (the reference's HalfFloat).
+float halfToFloat(uint16_t h);
+uint16_t floatToHalf(float f);
+
+/// A field as it is stored (the reference's HostCacheEntryType, Cache/HostCacheEntry.cpp): the native array is kept and
+/// the float view the calculators read is converted on first use -- b / 255.0f, s / 65535.0f, float(h)
+/// (HostCacheEntry.cpp:107-176).
 class HostCacheEntryType {
 public:
     HostCacheEntryType(size_t numEntries, float* dataOwned) : numEntries(numEntries), dataFloat(dataOwned) {}
-    ~HostCacheEntryType() { delete[] dataFloat; }
+    HostCacheEntryType(size_t numEntries, uint8_t* dataOwned)
+        : numEntries(numEntries), scalarDataFormatNative(ScalarDataFormat::BYTE), dataByte(dataOwned) {}
+    /// 16-bit storage: format is SHORT (unsigned 16 bit) or FLOAT16 (binary16 bit patterns).
+    HostCacheEntryType(size_t numEntries, ScalarDataFormat format, uint16_t* dataOwned);
+    ~HostCacheEntryType();
     HostCacheEntryType(const HostCacheEntryType&) = delete;
     HostCacheEntryType& operator=(const HostCacheEntryType&) = delete;
+    /// The float view (T = float is the only view the calculators use).
     template <class T>
-    const T* data() const { return reinterpret_cast<const T*>(dataFloat); }
+    const T* data() const { return reinterpret_cast<const T*>(getDataFloat()); }
     template <class T>
-    T dataAt(size_t idx) const { return T(dataFloat[idx]); }
+    T dataAt(size_t idx) const { return T(getDataFloatAt(idx)); }
     size_t getNumEntries() const { return numEntries; }
+    ScalarDataFormat getScalarDataFormatNative() const { return scalarDataFormatNative; }
+    const void* getDataNative() const;
+    const float* getDataFloat() const;
+    float getDataFloatAt(size_t idx) const;
+    /// FLOAT -> FLOAT16 only, as in the reference (HostCacheEntry.cpp:72-84); the float view stays as it is.
+    void switchNativeFormat(ScalarDataFormat newNativeFormat);
 
 private:
     size_t numEntries;
-    float* dataFloat;
+    ScalarDataFormat scalarDataFormatNative = ScalarDataFormat::FLOAT;
+    mutable float* dataFloat = nullptr;  // the native array of FLOAT, else the lazily converted view
+    uint8_t* dataByte = nullptr;
+    uint16_t* dataShort = nullptr;
+    uint16_t* dataFloat16 = nullptr;
 };
 typedef std::shared_ptr<HostCacheEntryType> HostCacheEntry;
 
@@ -69,6 +97,10 @@ public:
 
     /// Registers the data of one (field, time step, ensemble member): xs*ys*zs floats, copied.
     void setFieldData(const std::string& fieldName, int timeStepIdx, int ensembleIdx, const float* values);
+    /// The same for data in a native format: xs*ys*zs elements of `format` (uint8_t, uint16_t or binary16 bit patterns),
+    /// copied and kept as they are; calculators see the converted float view, the device receives the native array.
+    void setFieldData(const std::string& fieldName, int timeStepIdx, int ensembleIdx, ScalarDataFormat format,
+                      const void* values);
     std::vector<std::string> getFieldNames(FieldType) const;
 
     HostCacheEntry getFieldEntryCpu(FieldType fieldType, const std::string& fieldName, int timeStepIdx = -1,

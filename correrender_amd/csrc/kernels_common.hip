@@ -3,6 +3,9 @@
 //   * member min/max reduction     (getMinMaxScalarFieldValue per member + min/max over members,
 //                                   VolumeData.cpp:1632-1670, CorrelationCalculator.cpp:822-829)
 //   * synthetic box-ensemble fill  (recipe of scripts/generate_synth_box_ensembles.py:57-136; input generation only)
+#include <algorithm>
+
+#include "crf_device.h"
 #include "crf_internal.h"
 
 namespace crf {
@@ -18,6 +21,63 @@ hipError_t launch_gather_reference(const float* const* d_members, int cs, size_t
     const int block = 64;
     hipLaunchKernelGGL(gather_reference_kernel, dim3((cs + block - 1) / block), dim3(block), 0, s, d_members, cs,
                        voxel, d_out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Narrow member formats (crf_internal.h): the gather above with the conversion, and the fp32 copy of the members that
+// every kernel but the native Pearson field reads.  The copy is written once per set of members; plain loads and stores.
+template <int FMT>
+__global__ void gather_reference_narrow_kernel(const void* const* __restrict__ members, int cs, size_t voxel,
+                                               float* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < cs) out[c] = narrow_value<FMT>(members[c], voxel);
+}
+
+hipError_t launch_gather_reference_narrow(const void* const* d_narrow, int format, int cs, size_t voxel, float* d_out,
+                                          hipStream_t s) {
+    const dim3 grid((cs + 63) / 64), block(64);
+    switch (format) {
+        case CRF_MEMBER_U8:
+            hipLaunchKernelGGL(gather_reference_narrow_kernel<CRF_MEMBER_U8>, grid, block, 0, s, d_narrow, cs, voxel, d_out);
+            break;
+        case CRF_MEMBER_U16:
+            hipLaunchKernelGGL(gather_reference_narrow_kernel<CRF_MEMBER_U16>, grid, block, 0, s, d_narrow, cs, voxel, d_out);
+            break;
+        case CRF_MEMBER_F16:
+            hipLaunchKernelGGL(gather_reference_narrow_kernel<CRF_MEMBER_F16>, grid, block, 0, s, d_narrow, cs, voxel, d_out);
+            break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void widen_members_kernel(const void* const* __restrict__ members, size_t num_voxels,
+                                                            float* __restrict__ block, size_t stride) {
+    const void* src = members[blockIdx.y];
+    float* dst = block + size_t(blockIdx.y) * stride;
+    for (size_t i = size_t(blockIdx.x) * 256 + threadIdx.x; i < num_voxels; i += size_t(gridDim.x) * 256)
+        dst[i] = narrow_value<FMT>(src, i);
+}
+
+hipError_t launch_widen_members(const void* const* d_narrow, int format, int cs, size_t num_voxels, float* d_block,
+                                size_t stride, hipStream_t s) {
+    if (cs <= 0 || num_voxels == 0) return hipErrorInvalidValue;
+    const size_t blocks = std::min<size_t>((num_voxels + 255) / 256, 8192);
+    const dim3 grid{unsigned(blocks), unsigned(cs)}, block(256);
+    switch (format) {
+        case CRF_MEMBER_U8:
+            hipLaunchKernelGGL(widen_members_kernel<CRF_MEMBER_U8>, grid, block, 0, s, d_narrow, num_voxels, d_block, stride);
+            break;
+        case CRF_MEMBER_U16:
+            hipLaunchKernelGGL(widen_members_kernel<CRF_MEMBER_U16>, grid, block, 0, s, d_narrow, num_voxels, d_block, stride);
+            break;
+        case CRF_MEMBER_F16:
+            hipLaunchKernelGGL(widen_members_kernel<CRF_MEMBER_F16>, grid, block, 0, s, d_narrow, num_voxels, d_block, stride);
+            break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -719,6 +719,199 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_split_kernel(const flo
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Members in a narrow native format (crf_internal.h: u8, u16, f16): pearson_reg_kernel with the members kept as they
+// are in memory.  One lane owns the VPL = 4 (8-bit) or 2 (16-bit) consecutive voxels of one dword, so a wave's load of
+// one member is still 256 contiguous bytes, all cs loads are issued before the first use, and the cs raw dwords stay in
+// registers for the three passes: cs VGPRs for 2 or 4 voxels where the fp32 kernel needs cs per voxel.  Each pass
+// converts on use -- y_e - meanY recomputed in pass 3 from the same operands is the same float as the one pass 2 saw.
+// The integer formats' value x / 255.0f, x / 65535.0f is exact_div (crf_device.h) with a compile-time reciprocal: x is
+// an integer below 2^16 and the denominator a constant inside [2^-60, 2^60], its preconditions.  Everything is done
+// two voxels at a time in packed fp32 (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32: the same IEEE operation per element,
+// contraction off), as in pearson_split_kernel; the sequential sums are one chain per voxel, element-wise.
+// The caller passes `covered`, a multiple of VPL: no dword straddles the descriptor's end (a raw descriptor returns 0
+// for the WHOLE dword then); launch_pearson_narrow gives the up to VPL - 1 voxels behind it to the tail kernel.
+// Guarded slots (the last granule of a guarded instantiation) are stepped over in uniform branches, loads included: a
+// skipped slot is the +0 that pearson_reg_kernel adds for it in every pass.
+// ---------------------------------------------------------------------------------------------------------
+template <int FMT>
+constexpr int narrow_vpl() {
+    return FMT == CRF_MEMBER_U8 ? 4 : 2;
+}
+
+// voxels 2 h and 2 h + 1 of the lane out of a member's dword
+template <int FMT>
+__device__ __forceinline__ f2 narrow_pair(uint32_t w, int h) {
+    if constexpr (FMT == CRF_MEMBER_F16) {
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        const h2 v = __builtin_bit_cast(h2, w);
+        return f2{float(v[0]), float(v[1])};
+    } else {
+        constexpr float kDen = FMT == CRF_MEMBER_U8 ? 255.0f : 65535.0f;
+        constexpr float kRcp = 1.0f / kDen;
+        f2 x;
+        if constexpr (FMT == CRF_MEMBER_U8) {
+            x = f2{float((w >> (16 * h)) & 0xFFu), float((w >> (16 * h + 8)) & 0xFFu)};
+        } else {
+            x = f2{float(w & 0xFFFFu), float(w >> 16)};
+        }
+        const f2 rcp2 = {kRcp, kRcp}, den2 = {kDen, kDen};
+        const f2 q0 = x * rcp2;
+        const f2 rem = __builtin_elementwise_fma(-q0, den2, x);
+        return __builtin_elementwise_fma(rem, rcp2, q0);
+    }
+}
+
+template <int FMT, int CS_PAD, bool EXACT, int MIN_WAVES>
+__global__ __launch_bounds__(256, MIN_WAVES) void pearson_narrow_kernel(const void* const* __restrict__ members,
+                                                                        const float* __restrict__ prep,
+                                                                        float* __restrict__ out, uint32_t covered,
+                                                                        int cs, int out_vector) {
+    static_assert(CS_PAD <= kPrepZeroFilled, "a_e is zero-filled up to kPrepZeroFilled");
+    constexpr int VPL = narrow_vpl<FMT>(), P = VPL / 2;  // voxels, and pairs of voxels, per lane
+    constexpr int kFirstGuarded = EXACT ? CS_PAD : CS_PAD - pad_granule(CS_PAD);
+    // slot e is a member iff e < mine.  (Laundered before each pass: left alone the compiler evaluates the guarded slots'
+    // tests once and keeps them as SGPR pairs across the kernel, which spill into VGPR lanes; see pearson_split_kernel.)
+    int mine = cs;
+    const auto is_member = [&mine](int e) { return e < kFirstGuarded || e < mine; };
+    const uint32_t dword = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t v0 = dword * VPL;
+    const uint32_t byte_offset = dword * 4u;
+    const uint32_t bytes = covered / VPL * 4u;  // descriptor bound: lanes past the end read 0 and store nothing
+    uint32_t w[CS_PAD];
+#pragma unroll
+    for (int e = 0; e < CS_PAD; e++) {
+        w[e] = 0u;
+        if (is_member(e)) {  // a uniform branch around each of the few guarded loads (they are the last loads issued)
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(members[e]), short(0), int(bytes), 0x00020000);
+            w[e] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, int(byte_offset), 0, kAuxNonTemporal);
+        }
+    }
+    const float n = float(cs);
+    const float invN = 1.0f / n;
+    const float invNm1 = 1.0f / (n - 1.0f);
+    const f2 zero2 = {0.0f, 0.0f};
+    // pass 1: meanY += invN * y_e
+    f2 meanY[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) meanY[p] = zero2;
+    {
+        const f2 scale = {invN, invN};
+#pragma unroll
+        for (int e = 0; e < CS_PAD; e++) {
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (!is_member(e)) continue;  // uniform
+                meanY[p] += scale * narrow_pair<FMT>(w[e], p);
+            }
+            if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // (else the conversions of many slots run ahead)
+        }
+    }
+    // Laundered before each pass: left alone the compiler keeps the converted values of pass 1 for the later passes --
+    // cs x VPL registers, the fp32 kernel's footprint, which is what this kernel exists to avoid.
+    const auto launder = [&w, &mine]() {
+#pragma unroll
+        for (int e = 0; e < CS_PAD; e++) asm volatile("" : "+v"(w[e]));
+        asm volatile("" : "+s"(mine));
+    };
+    launder();
+    // pass 2: varY += (invNm1 * d_e) * d_e, d_e = y_e - meanY
+    f2 varY[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) varY[p] = zero2;
+    {
+        const f2 scale = {invNm1, invNm1};
+#pragma unroll
+        for (int e = 0; e < CS_PAD; e++) {
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (!is_member(e)) continue;  // uniform
+                const f2 d = narrow_pair<FMT>(w[e], p) - meanY[p];
+                varY[p] += (scale * d) * d;
+            }
+            if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    launder();
+    f2 sdY[P], r[P];
+    bool guard = true;
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        sdY[p] = f2{sqrtf(varY[p][0]), sqrtf(varY[p][1])};
+        r[p] = zero2;
+        guard = guard && exact_div_guard(meanY[p][0], sdY[p][0]) && exact_div_guard(meanY[p][1], sdY[p][1]);
+    }
+    // pass 3: r += a_e * (d_e / sdY)
+    if (__all(guard)) {  // exact quotients through one reciprocal per voxel (crf_device.h: exact_div)
+        f2 rcp[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) rcp[p] = f2{1.0f / sdY[p][0], 1.0f / sdY[p][1]};
+#pragma unroll
+        for (int e = 0; e < CS_PAD; e++) {
+            const float a = prep[e];
+            const f2 a2 = {a, a};
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (!is_member(e)) continue;  // uniform
+                const f2 d = narrow_pair<FMT>(w[e], p) - meanY[p];
+                const f2 q0 = d * rcp[p];
+                const f2 rem = __builtin_elementwise_fma(-q0, sdY[p], d);
+                r[p] += a2 * __builtin_elementwise_fma(rem, rcp[p], q0);
+            }
+            if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < CS_PAD; e++) {
+            const float a = prep[e];
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (!is_member(e)) continue;  // uniform
+                const f2 y = narrow_pair<FMT>(w[e], p);
+#pragma unroll
+                for (int i = 0; i < 2; i++) r[p][i] += a * ((y[i] - meanY[p][i]) / sdY[p][i]);
+            }
+            if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (v0 + VPL <= covered) {
+        if (out_vector) {
+            typedef float fv __attribute__((ext_vector_type(VPL)));
+            fv v;
+#pragma unroll
+            for (int i = 0; i < VPL; i++) v[i] = r[i / 2][i % 2];
+            __builtin_nontemporal_store(v, reinterpret_cast<fv*>(out + v0));
+        } else {
+#pragma unroll
+            for (int i = 0; i < VPL; i++) store_result_nt(out + v0 + i, r[i / 2][i % 2]);
+        }
+    }
+}
+
+// the up to VPL - 1 voxels behind the last whole dword of the narrow members: one voxel per lane, three passes
+template <int FMT>
+__global__ __launch_bounds__(64) void pearson_narrow_tail_kernel(const void* const* __restrict__ members,
+                                                                 const float* __restrict__ prep,
+                                                                 float* __restrict__ out, size_t voxel_offset,
+                                                                 size_t voxel_end, int cs) {
+    const size_t v0 = voxel_offset + size_t(blockIdx.x) * 64 + threadIdx.x;
+    if (v0 >= voxel_end) return;
+    const float n = float(cs);
+    const float invN = 1.0f / n;
+    const float invNm1 = 1.0f / (n - 1.0f);
+    float meanY = 0.0f;
+    for (int e = 0; e < cs; e++) meanY += invN * narrow_value<FMT>(members[e], v0);
+    float varY = 0.0f;
+    for (int e = 0; e < cs; e++) {
+        const float d = narrow_value<FMT>(members[e], v0) - meanY;
+        varY += invNm1 * d * d;
+    }
+    const float sdY = sqrtf(varY);
+    float r = 0.0f;
+    for (int e = 0; e < cs; e++) r += prep[e] * ((narrow_value<FMT>(members[e], v0) - meanY) / sdY);
+    store_result_nt(out + v0, r);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Symmetric field mode (CorrelationFieldMode::SEPARATE_SYMMETRIC, CorrelationMain.glsl:10-15): voxel v correlates
 // the reference field's members at v with the query field's members at v -- computePearson2 on two arrays
 // (Correlation.cpp:141-174), nothing to hoist.  2*cs loads per voxel (8*cs + 4 algorithmic bytes), both sides in
@@ -1080,6 +1273,73 @@ hipError_t launch_pearson_symmetric(const float* const* d_members_ref, const flo
         case 7: launch_symmetric<112>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
         default: launch_symmetric<128>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
     }
+    return hipGetLastError();
+}
+
+namespace {
+// occupancy request.  Registers: CS_PAD raw dwords + the working set of one pair of voxels (16-bit formats) or two
+// (8-bit), each instantiation at the most waves per SIMD it reaches without scratch (tools/resource_usage.py).
+constexpr int narrow_min_waves(int format, int cs_pad, bool exact) {
+    if (format == CRF_MEMBER_U8) return cs_pad <= 32 ? 4 : cs_pad <= 48 || (cs_pad == 64 && exact) ? 3 : 2;
+    return cs_pad <= 64 ? 4 : cs_pad <= 96 ? 3 : 2;
+}
+
+template <int FMT, int CS_PAD>
+void launch_narrow(const void* const* d_narrow, const float* d_prep, float* d_out, size_t covered, int cs, bool out_vector,
+                   hipStream_t s) {
+    const size_t per_block = size_t(256) * narrow_vpl<FMT>();
+    const dim3 grid(unsigned((covered + per_block - 1) / per_block)), block(256);
+    if (cs == CS_PAD)
+        hipLaunchKernelGGL((pearson_narrow_kernel<FMT, CS_PAD, true, narrow_min_waves(FMT, CS_PAD, true)>), grid, block, 0,
+                           s, d_narrow, d_prep, d_out, uint32_t(covered), cs, out_vector ? 1 : 0);
+    else
+        hipLaunchKernelGGL((pearson_narrow_kernel<FMT, CS_PAD, false, narrow_min_waves(FMT, CS_PAD, false)>), grid, block,
+                           0, s, d_narrow, d_prep, d_out, uint32_t(covered), cs, out_vector ? 1 : 0);
+}
+
+template <int FMT>
+void launch_narrow_format(const void* const* d_narrow, const float* d_prep, float* d_out, size_t num_voxels, int cs,
+                          bool out_vector, hipStream_t s) {
+    const size_t covered = num_voxels / narrow_vpl<FMT>() * narrow_vpl<FMT>();
+    if (covered > 0) {
+        switch (cs <= 8 ? 8 : (cs + 15) / 16 * 16) {
+            case 8: launch_narrow<FMT, 8>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            case 16: launch_narrow<FMT, 16>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            case 32: launch_narrow<FMT, 32>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            case 48: launch_narrow<FMT, 48>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            case 64: launch_narrow<FMT, 64>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            case 80: launch_narrow<FMT, 80>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            case 96: launch_narrow<FMT, 96>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            case 112: launch_narrow<FMT, 112>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+            default: launch_narrow<FMT, 128>(d_narrow, d_prep, d_out, covered, cs, out_vector, s); break;
+        }
+    }
+    if (covered < num_voxels)
+        hipLaunchKernelGGL(pearson_narrow_tail_kernel<FMT>, dim3(1), dim3(64), 0, s, d_narrow, d_prep, d_out, covered,
+                           num_voxels, cs);
+}
+}  // namespace
+
+hipError_t launch_pearson_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, bool out_vector,
+                                 const RefSource& ref, float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin,
+                                 hipEvent_t ev_end, LaunchInfo* info) {
+    if (cs < 2 || cs > kNarrowMaxMembers || format == CRF_MEMBER_F32 ||
+        num_voxels * member_format_bytes(format) >= kNarrowMaxBytes)
+        return hipErrorInvalidValue;
+    if (ref.prepare()) {
+        if (!ref.values) return hipErrorInvalidValue;  // the caller gathers the converted reference values
+        hipLaunchKernelGGL(pearson_prep_kernel, dim3(1), dim3(256), size_t(cs) * sizeof(float), s, ref, nullptr, cs, d_prep);
+    }
+    if (!ref.run()) return hipGetLastError();
+    if (ev_begin) (void)hipEventRecord(ev_begin, s);
+    switch (format) {
+        case CRF_MEMBER_U8: launch_narrow_format<CRF_MEMBER_U8>(d_narrow, d_prep, d_out, num_voxels, cs, out_vector, s); break;
+        case CRF_MEMBER_U16: launch_narrow_format<CRF_MEMBER_U16>(d_narrow, d_prep, d_out, num_voxels, cs, out_vector, s); break;
+        case CRF_MEMBER_F16: launch_narrow_format<CRF_MEMBER_F16>(d_narrow, d_prep, d_out, num_voxels, cs, out_vector, s); break;
+        default: return hipErrorInvalidValue;
+    }
+    if (info) info->kernel_name = "pearson_narrow_kernel";
+    if (ev_end) (void)hipEventRecord(ev_end, s);
     return hipGetLastError();
 }
 

@@ -33,6 +33,17 @@ MEASURE_IDS = ["pearson", "spearman", "kendall", "mi_binned", "mi_kraskov",
                "binned_mi_correlation_coefficient", "kmi_correlation_coefficient"]
 # crf_member_layout (include/corrfield.h)
 MEMBER_LAYOUTS = ["auto", "raw", "packed"]
+# crf_member_format (include/corrfield.h): the native formats of the primary members
+MEMBER_FORMATS = ["f32", "u8", "u16", "f16"]
+
+
+def _member_format(dtype) -> int:
+    """crf_member_format of a numpy or torch dtype; anything but float32, uint8, uint16 and float16 raises."""
+    name = str(dtype).replace("torch.", "")
+    try:
+        return {"float32": 0, "uint8": 1, "uint16": 2, "float16": 3}[name]
+    except KeyError:
+        raise TypeError(f"members of dtype {dtype} are not supported: float32, float16, uint16 or uint8") from None
 
 
 def default_kraskov_k(cs: int) -> int:
@@ -88,22 +99,53 @@ class CorrField:
         self._keepalive = None
 
     def upload_members(self, members: Sequence[np.ndarray]):
-        """members: cs host arrays of zs*ys*xs float32 (any shape, C-contiguous, x fastest)."""
-        arrs = [np.ascontiguousarray(m, dtype=np.float32) for m in members]
+        """members: cs host arrays of zs*ys*xs elements (any shape, C-contiguous, x fastest).  Arrays that are all
+        float16, uint16 or uint8 stay in that format on the device (value = float(h), s / 65535, b / 255: the reference's
+        HostCacheEntry::data<float>()) -- such arrays are no longer cast by value.  Any other dtype, or a mix of dtypes,
+        is converted to float32 by value on the host as before (float64 input stays a convenience; bind_members, which
+        cannot convert, raises instead)."""
+        dtypes = {np.asarray(m).dtype for m in members}
+        narrow = len(dtypes) == 1 and next(iter(dtypes)) in (np.dtype(np.float16), np.dtype(np.uint16), np.dtype(np.uint8))
+        dtype = next(iter(dtypes)) if narrow else np.dtype(np.float32)
+        arrs = [np.ascontiguousarray(m, dtype=dtype) for m in members]
         if len(arrs) != self.cs or any(a.size != self.num_voxels for a in arrs):
             raise ValueError("members do not match the grid declared with set_grid")
         ptrs = (C.c_void_p * self.cs)(*[a.ctypes.data for a in arrs])
-        self._check(self._lib.crf_upload_members(self._ctx, ptrs))
+        if narrow:
+            self._check(self._lib.crf_upload_members_format(self._ctx, _member_format(dtype), ptrs))
+        else:
+            self._check(self._lib.crf_upload_members(self._ctx, ptrs))
 
     def bind_members(self, members):
-        """members: cs torch CUDA float32 tensors (or one [cs, ...] tensor), each holding one volume; borrowed."""
+        """members: cs torch CUDA tensors (or one [cs, ...] tensor), each holding one volume; borrowed.  The dtype decides
+        the member format: float32, or float16 / uint16 / uint8 read natively (see upload_members); any other raises.
+        The native Pearson kernel loads whole dwords, so every narrow member must start on a 4-byte boundary: the rows of
+        a plain [cs, n] uint8 or 16-bit tensor do only when n * itemsize is a multiple of 4.  Otherwise every evaluation,
+        the Pearson field included, runs on the fp32 copy (cs * n floats of device memory; last_member_format() says
+        "f32") -- pad the row stride, or use upload_members, whose copy is aligned."""
         tensors = [members[i] for i in range(self.cs)]
+        formats = {_member_format(t.dtype) for t in tensors}
+        if len(formats) != 1:
+            raise TypeError("every member must have the same dtype")
+        fmt = formats.pop()
         for t in tensors:
-            if not t.is_cuda or not t.is_contiguous() or t.numel() != self.num_voxels or t.element_size() != 4:
-                raise ValueError("each member must be a contiguous CUDA float32 tensor of xs*ys*zs elements")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() != self.num_voxels:
+                raise ValueError("each member must be a contiguous CUDA tensor of xs*ys*zs elements")
         ptrs = (C.c_void_p * self.cs)(*[t.data_ptr() for t in tensors])
-        self._check(self._lib.crf_bind_members_device(self._ctx, ptrs))
+        if fmt == 0:
+            self._check(self._lib.crf_bind_members_device(self._ctx, ptrs))
+        else:
+            self._check(self._lib.crf_bind_members_device_format(self._ctx, fmt, ptrs))
         self._keepalive = (members, tensors)
+
+    def member_format(self) -> str:
+        """"f32", "u8", "u16" or "f16": the format of the bound primary members."""
+        return MEMBER_FORMATS[self._lib.crf_member_format(self._ctx)]
+
+    def last_member_format(self) -> str:
+        """The format the per-voxel kernel of the last field evaluation read: the members' own when the Pearson field
+        read narrow members natively, "f32" when it ran on fp32 members or on the fp32 copy of narrow ones."""
+        return MEMBER_FORMATS[self._lib.crf_last_member_format(self._ctx)]
 
     def member_minmax(self):
         mn, mx = C.c_float(), C.c_float()

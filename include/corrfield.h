@@ -19,7 +19,9 @@
  *   - the *_device entry points are asynchronous on the stream they are given, but a context owns ONE set of scratch
  *     buffers (reference vector, reference-side tables, deferred-voxel list, workspace): at most one evaluation per
  *     context may be in flight at a time unless consecutive calls are ordered on the same stream (or by events).  The
- *     only state meant for overlap across streams are the prepared slots of crf_prepare_device.  crf_set_grid and any
+ *     only state meant for overlap across streams are the prepared slots of crf_prepare_device (given a reference
+ *     VECTOR; a reference POINT on members in a narrow format is gathered through the one reference-vector buffer, so
+ *     such preparations must be ordered like any other evaluation).  crf_set_grid and any
  *     call that has to grow a scratch buffer synchronise the device first.
  *   - crf_compute (host output) of a result of 8 MiB or more evaluates the grid in voxel ranges on TWO streams of the
  *     context, so the scratch that the per-voxel kernels write (deferred-voxel list with its counter, workspace) exists
@@ -124,7 +126,9 @@ void crf_destroy(crf_context* ctx);
 /* Last error message of this context (or of the calling thread's last failed crf_create when ctx==NULL). */
 const char* crf_last_error(const crf_context* ctx);
 /* ABI version of this header, bumped on incompatible change. */
-int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_minmax_divergent;
+int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_minmax_divergent; added since, compatibly:
+                                  crf_upload_members_format, crf_bind_members_device_format, crf_member_format,
+                                  crf_last_member_format;
                                4: crf_group_* (several devices behind one caller thread), crf_set_kraskov_noise;
                                3: crf_params.reserved[0] became prepared_slot (same layout; 0 keeps the old meaning) */
 
@@ -136,6 +140,33 @@ int crf_set_grid(crf_context* ctx, int xs, int ys, int zs, int cs);
 int crf_upload_members(crf_context* ctx, const float* const* host_members);
 /* Uses cs caller-owned DEVICE volumes in place (borrowed until the next set_grid/upload/bind/destroy). */
 int crf_bind_members_device(crf_context* ctx, const void* const* device_members);
+/* ---- primary members in a narrow native format -------------------------------------------------------------------
+ * The reference keeps scalar fields as float, unsigned byte, unsigned short or float16 (format_cast,
+ * src/Loaders/DataSetList.cpp:185-195) and its calculators see them through HostCacheEntry::data<float>()
+ * (src/Volume/Cache/HostCacheEntry.cpp:107-176); the value of an element is given below.  Members in such a format
+ * stay as narrow in HBM as they are on the host.  Every entry point that reads the primary members gives exactly the
+ * result of the same call on fp32 members that hold those values.
+ *   - The Pearson field (CRF_PEARSON without CRF_FLAG_SYMMETRIC) at 2..128 members reads the narrow members directly
+ *     (pearson_narrow_kernel); crf_last_member_format then returns the narrow format and crf_last_member_layout RAW
+ *     (crf_set_member_layout has no effect on narrow members: the packed copy is an fp32 format).
+ *   - Everything else runs on an fp32 copy of the members that the context builds on the compute stream at the first
+ *     call that needs it (one owned block of cs x xs*ys*zs floats; CRF_ERR_DEVICE naming the copy and its size if it
+ *     cannot be allocated) and drops in crf_set_grid, upload, bind and crf_members_changed; crf_last_member_format then
+ *     returns CRF_MEMBER_F32.  So does the Pearson field over borrowed members that are not all 4-byte aligned.
+ *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.  Secondary members are fp32 only.
+ *     crf_group_* evaluations on a context that holds narrow members: CRF_ERR_UNSUPPORTED.
+ * format == CRF_MEMBER_F32 behaves exactly like crf_upload_members / crf_bind_members_device, which set the format to
+ * CRF_MEMBER_F32. */
+enum crf_member_format { /* a tag only: the function crf_member_format() below shares the name */
+    CRF_MEMBER_F32 = 0,
+    CRF_MEMBER_U8 = 1,   /* value = float(b) / 255.0f */
+    CRF_MEMBER_U16 = 2,  /* value = float(s) / 65535.0f */
+    CRF_MEMBER_F16 = 3   /* value = float(h), IEEE binary16 */
+};
+int crf_upload_members_format(crf_context* ctx, int format, const void* const* host_members);
+int crf_bind_members_device_format(crf_context* ctx, int format, const void* const* device_members);
+int crf_member_format(const crf_context* ctx);      /* format of the bound primary members */
+int crf_last_member_format(const crf_context* ctx); /* format the per-voxel kernel of the last field evaluation read */
 /* min of per-member minima / max of per-member maxima over the local grid (CorrelationCalculator.cpp:822-829 on
  * top of VolumeData::getMinMaxScalarFieldValue, VolumeData.cpp:1632-1670); computed on the device, cached until
  * the members change. */
