@@ -55,6 +55,9 @@ hipError_t launch_gather_reference_rows(const float* const* d_members, int cs, c
 hipError_t launch_minmax(const float* const* d_members, int cs, size_t num_voxels, uint32_t* d_keys /*[2]*/,
                          hipStream_t s);
 float minmax_key_to_float(uint32_t key);
+// the whole evaluation at one member: fills d_out with 1 (fill_kernel) if ref.run()
+hipError_t launch_single_member(const RefSource& ref, float* d_out, size_t num_voxels, hipStream_t s,
+                                hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 hipError_t launch_synth_box_member(float* d_out, int xs, int ys, int zs_local, int z_begin, int zs_global, int c,
                                    int cs, uint64_t seed, hipStream_t s);
 

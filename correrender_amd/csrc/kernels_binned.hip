@@ -475,18 +475,11 @@ void launch_binned_prep(const RefSource& ref, const float* const* d_members, int
                        a.num_bins, a.min_ref, a.max_ref, tableT, d_prep);
 }
 
-
+// O(cs) histogram kernel for any member count; hipErrorNotSupported when num_bins is too large for its LDS rows
 hipError_t launch_mi_binned_hist(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                                  const BinnedArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
                                  hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
-    if (cs == 1) {
-        if (!ref.run()) return hipSuccess;
-        if (ev_begin) (void)hipEventRecord(ev_begin, s);
-        hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
-        if (ev_end) (void)hipEventRecord(ev_end, s);
-        if (info) info->kernel_name = "fill_kernel";
-        return e;
-    }
+    if (cs == 1) return launch_single_member(ref, d_out, num_voxels, s, ev_begin, ev_end, info);
     const size_t rows = size_t(a.num_bins) * 64 * 6;
     if (rows > 56 * 1024 || size_t(2 * cs + 1) * sizeof(int) > kBinnedSxOffset) return hipErrorNotSupported;
     int* prep = reinterpret_cast<int*>(d_prep);
@@ -511,14 +504,7 @@ hipError_t launch_mi_binned_hist(const float* const* d_members, int cs, size_t n
 hipError_t launch_mi_binned(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                             const BinnedArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
                             hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
-    if (cs == 1) {
-        if (!ref.run()) return hipSuccess;
-        if (ev_begin) (void)hipEventRecord(ev_begin, s);
-        hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
-        if (ev_end) (void)hipEventRecord(ev_end, s);
-        if (info) info->kernel_name = "fill_kernel";
-        return e;
-    }
+    if (cs == 1) return launch_single_member(ref, d_out, num_voxels, s, ev_begin, ev_end, info);
     const int n_pad = (cs + 15) / 16 * 16;
     int* prep = reinterpret_cast<int*>(d_prep);
     const double* tableT = d_tables + (cs + 1);
@@ -543,5 +529,4 @@ hipError_t launch_mi_binned(const float* const* d_members, int cs, size_t num_vo
     return hipGetLastError();
 }
 
-// any cs (tables must fit LDS: cs <= 2048), k <= 128; hipErrorNotSupported otherwise
 }  // namespace crf

@@ -172,6 +172,18 @@ hipError_t launch_minmax(const float* const* d_members, int cs, size_t num_voxel
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// One member: every estimator's field is 1 by the reference's convention (CorrelationCalculator.cpp:882-885).
+hipError_t launch_single_member(const RefSource& ref, float* d_out, size_t num_voxels, hipStream_t s,
+                                hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    if (!ref.run()) return hipSuccess;
+    if (ev_begin) (void)hipEventRecord(ev_begin, s);
+    hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
+    if (ev_end) (void)hipEventRecord(ev_end, s);
+    if (info) info->kernel_name = "fill_kernel";
+    return e;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Synthetic "box ensemble".  lambda(x,y,z) = sum over 10 boxes of peak(chebyshev((x,y,z)-(cx,cy,zs/2)) / (size/2)),
 // peak(u) = 0 for u >= 1 else 1 - max(0, 2|u|-1)^2  (generate_synth_box_ensembles.py:57-61,70-102, with g = xs/8
 // for our grids; the original uses xs=ys=128, zs=32, g=16).  Sample of member c at a voxel:

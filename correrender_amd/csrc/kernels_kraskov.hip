@@ -24,10 +24,8 @@
 
 #include "crf_device.h"
 #include "crf_internal.h"
-
-#include <cstdlib>
-
 #include "crf_mi_device.h"
+#include "kraskov_plan.h"
 
 namespace crf {
 
@@ -38,7 +36,6 @@ namespace crf {
 //                   [cs, 2cs) the same values sorted ascending (the reference sorts them for its 1-D range counts,
 //                   MutualInformation.cpp:187; voxel independent, so sorted once per evaluation)
 // the distance table lies in the preparation buffer behind the two coordinate vectors (up to 128 members: 133 KB)
-constexpr int kDxtMaxMembers = 128;
 __host__ __device__ inline int dxt_offset(int cs) { return (2 * cs + 7) / 8 * 8; }  // in doubles
 static_assert(size_t(((2 * kDxtMaxMembers + 7) / 8 * 8) + 128 * 128) * sizeof(double) <= kPrepBytes - 16, "prep buffer");
 
@@ -129,8 +126,8 @@ __device__ __forceinline__ void count_less_batch(const double* tab, int n, int t
     }
 }
 
-// K > 0: the K = k nearest OTHER points are kept in registers (sorted insertion: min/max only).  K == 0: any k,
-// selection by repeated minimum passes.  TI points are processed concurrently per lane.
+// The K = k <= 4 nearest OTHER points are kept in registers (sorted insertion: min/max only; a kd-tree returns at most
+// cs points, so the host passes K = min(k, cs - 1)).  TI points are processed concurrently per lane.
 template <int K, int TI, bool DXT = false>
 __global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __restrict__ members,
                                                         const double* __restrict__ prep_px,
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __re
     }
     __syncthreads();
 
-    const int kk = k < cs - 1 ? k : cs - 1;  // neighbours besides the point itself (a kd-tree returns at most cs points)
+    const int last = cs - 1;  // the surplus points of the last sweep repeat it
     int top = 1;
     while (top * 2 <= cs) top *= 2;
     const double factor = 1.0 / double(cs);
@@ -174,7 +171,7 @@ __global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __re
         double pxi[TI], pyi[TI], rx[TI], ry[TI];
 #pragma unroll
         for (int t = 0; t < TI; t++) {
-            const int ii = (i0 + t < cs) ? i0 + t : cs - 1;
+            const int ii = (i0 + t < cs) ? i0 + t : last;
             pxi[t] = s_px[ii];
             pyi[t] = double(s_y[ii * 64 + lane]) + s_nq[ii];
         }
@@ -182,19 +179,38 @@ __global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __re
         // ---- pass A: Chebyshev distance to the k-th neighbour (the (k+1)-th smallest distance including the zero
         //      distance to the point itself, MutualInformation.cpp:430-434)
         double dk[TI];
-        if constexpr (K > 0) {
-            double best[TI][K];
+        double best[TI][K];
 #pragma unroll
-            for (int t = 0; t < TI; t++)
+        for (int t = 0; t < TI; t++)
 #pragma unroll
-                for (int q = 0; q < K; q++) best[t][q] = inf;
-            auto visit = [&](int j, bool may_be_self) {
-                const double pxj = s_px[j];
+            for (int q = 0; q < K; q++) best[t][q] = inf;
+        auto visit = [&](int j, bool may_be_self) {
+            const double pxj = s_px[j];
+            const double pyj = double(s_y[j * 64 + lane]) + s_nq[j];
+#pragma unroll
+            for (int t = 0; t < TI; t++) {
+                double d = chebyshev_f64(pxi[t] - pxj, pyi[t] - pyj);
+                if (may_be_self) d = (j == i0 + t) ? inf : d;
+#pragma unroll
+                for (int q = 0; q < K; q++) {
+                    const double lo = min_f64(best[t][q], d);
+                    if (q + 1 < K) d = max_f64(best[t][q], d);
+                    best[t][q] = lo;
+                }
+            }
+        };
+        if constexpr (DXT) {
+            // x distances from the prepared table (scalar loads; its diagonal excludes the point itself): see
+            // kraskov_direct_kernel
+            const double* dx_col = prep_px + dxt_offset(cs) + i0;
+            const int dxt_cols = (cs + 7) / 8 * 8;
+#pragma unroll 2
+            for (int j = 0; j < cs; j++) {
                 const double pyj = double(s_y[j * 64 + lane]) + s_nq[j];
+                const double* dx_row = dx_col + size_t(j) * size_t(dxt_cols);
 #pragma unroll
                 for (int t = 0; t < TI; t++) {
-                    double d = chebyshev_f64(pxi[t] - pxj, pyi[t] - pyj);
-                    if (may_be_self) d = (j == i0 + t) ? inf : d;
+                    double d = chebyshev_f64_sx(pyi[t] - pyj, dx_row[t]);
 #pragma unroll
                     for (int q = 0; q < K; q++) {
                         const double lo = min_f64(best[t][q], d);
@@ -202,63 +218,17 @@ __global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __re
                         best[t][q] = lo;
                     }
                 }
-            };
-            if constexpr (DXT) {
-                // x distances from the prepared table (scalar loads; its diagonal excludes the point itself): see
-                // kraskov_direct_kernel
-                const double* dx_col = prep_px + dxt_offset(cs) + i0;
-                const int dxt_cols = (cs + 7) / 8 * 8;
-#pragma unroll 2
-                for (int j = 0; j < cs; j++) {
-                    const double pyj = double(s_y[j * 64 + lane]) + s_nq[j];
-                    const double* dx_row = dx_col + size_t(j) * size_t(dxt_cols);
-#pragma unroll
-                    for (int t = 0; t < TI; t++) {
-                        double d = chebyshev_f64_sx(pyi[t] - pyj, dx_row[t]);
-#pragma unroll
-                        for (int q = 0; q < K; q++) {
-                            const double lo = min_f64(best[t][q], d);
-                            if (q + 1 < K) d = max_f64(best[t][q], d);
-                            best[t][q] = lo;
-                        }
-                    }
-                }
-            } else {
+            }
+        } else {
 #pragma unroll 2
             for (int j = 0; j < i0; j++) visit(j, false);
 #pragma unroll 1
             for (int j = i0; j < i1; j++) visit(j, true);
 #pragma unroll 2
             for (int j = i1; j < cs; j++) visit(j, false);
-            }
-#pragma unroll
-            for (int t = 0; t < TI; t++) dk[t] = best[t][K - 1];
-        } else {
-#pragma unroll
-            for (int t = 0; t < TI; t++) {
-                double cur = -1.0, m = 0.0;
-                int cnt = 0;
-#pragma unroll 1
-                for (int pass = 0; pass < kk; pass++) {
-                    m = inf;
-                    int c = 0;
-#pragma unroll 2
-                    for (int j = 0; j < cs; j++) {
-                        const double pxj = s_px[j];
-                        const double pyj = double(s_y[j * 64 + lane]) + s_nq[j];
-                        const double d = fmax(fabs(pxi[t] - pxj), fabs(pyi[t] - pyj));
-                        if (d > cur && j != i0 + t) {
-                            c = (d < m) ? 1 : (d == m ? c + 1 : c);
-                            m = fmin(m, d);
-                        }
-                    }
-                    cnt += c;
-                    if (cnt >= kk) break;
-                    cur = m;
-                }
-                dk[t] = m;
-            }
         }
+#pragma unroll
+        for (int t = 0; t < TI; t++) dk[t] = best[t][K - 1];
         // ---- search radii
         if (estimator == 1) {
 #pragma unroll
@@ -875,192 +845,169 @@ __global__ __launch_bounds__(64 * NW, sorted_min_waves(K, NS)) void kraskov_sort
     }
 }
 
-// LDS of kraskov_direct_kernel's partial sums: 16 (tile, wave) slots x 64 lanes x (2 doubles + 1 int)
-constexpr size_t kDirectSumBytes = 16 * 64 * (2 * sizeof(double) + sizeof(int));
-
-static int direct_share_tiles() {
-    const char* e = getenv("CRF_KRASKOV_SHARE");  // tuning: 0 = a voxel tile per wave (the round-1 work split)
-    return !(e && e[0] == '0');
-}
-
+// ---------------------------------------------------------------------------------------------------------------
+// Host side.  kraskov_plan.h decides which instantiation runs; the lookups below turn its plan into a kernel pointer.
+// ---------------------------------------------------------------------------------------------------------------
 void launch_kraskov_prep(const RefSource& ref, const float* const* d_members, int cs, const double* noise_ref,
                          double* d_prep, hipStream_t s) {
     hipLaunchKernelGGL(kraskov_prep_kernel, dim3(1), dim3(256), size_t(cs) * sizeof(double), s, ref, d_members, cs,
                        noise_ref, d_prep);
 }
 
-// O(cs) histogram kernel for any member count; hipErrorNotSupported when num_bins is too large for its LDS rows
+namespace {
 
-hipError_t launch_mi_kraskov_direct(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
-                                    const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out,
-                                    hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
-    const int kk = a.k < cs - 1 ? a.k : cs - 1;
-    const size_t lds = size_t(3 * cs) * sizeof(double);
-    if (kk > 128 || lds + kDirectSumBytes > 60 * 1024) return hipErrorNotSupported;
-    const double* psi = d_tables;
+// mi_kraskov_kernel and kraskov_sorted_kernel: (members, prep, psi, noise_query, out, num_voxels, cs, k, estimator, to_cc,
+// c_term); kraskov_direct_kernel: members_x after members, share after c_term
+using TileKernel = void (*)(const float* const*, const double*, const double*, const double*, float*, size_t, int, int,
+                            int, int, double);
+using DirectKernel = void (*)(const float* const*, const float* const*, const double*, const double*, const double*,
+                              float*, size_t, int, int, int, int, double, int);
+
+TileKernel column_kernel(const KraskovPlan& p) {
+    switch (p.K) {
+        case 1: return p.dxt ? mi_kraskov_kernel<1, 8, true> : mi_kraskov_kernel<1, 8>;
+        case 2:
+            if (p.TI == 16) return mi_kraskov_kernel<2, 16>;
+            return p.dxt ? mi_kraskov_kernel<2, 8, true> : mi_kraskov_kernel<2, 8>;
+        case 3:
+            if (p.TI == 16) return mi_kraskov_kernel<3, 16>;
+            return p.dxt ? mi_kraskov_kernel<3, 8, true> : mi_kraskov_kernel<3, 8>;
+        default: return p.dxt ? mi_kraskov_kernel<4, 4, true> : mi_kraskov_kernel<4, 4>;
+    }
+}
+
+template <int NS>
+TileKernel sorted_kernel_k(int K) {
+    switch (K) {
+        case 1: return kraskov_sorted_kernel<1, NS, 2>;
+        case 2: return kraskov_sorted_kernel<2, NS, 2>;
+        case 3: return kraskov_sorted_kernel<3, NS, 2>;
+        default: return kraskov_sorted_kernel<4, NS, 2>;
+    }
+}
+
+TileKernel sorted_kernel(const KraskovPlan& p) {
+    return p.NS == 32 ? sorted_kernel_k<32>(p.K) : p.NS == 48 ? sorted_kernel_k<48>(p.K) : sorted_kernel_k<64>(p.K);
+}
+
+// with the x-distance table: K = k <= 4; the staged form always takes 4 points per sweep
+template <int K>
+DirectKernel direct_table_kernel_k(const KraskovPlan& p) {
+    if (p.stage) return kraskov_direct_kernel<K, 4, false, true, true>;
+    return p.TI == 4 ? kraskov_direct_kernel<K, 4, false, true> : kraskov_direct_kernel<K, 8, false, true>;
+}
+
+template <bool SYM>
+DirectKernel direct_plain_kernel(const KraskovPlan& p) {
+    if constexpr (!SYM) {  // the symmetric mode has neither the 4-point sweeps at K = 3, 4 nor K = 128
+        if (p.K == 3 && p.TI == 4) return kraskov_direct_kernel<3, 4>;
+        if (p.K == 4 && p.TI == 4) return kraskov_direct_kernel<4, 4>;
+        if (p.K == 128) return kraskov_direct_kernel<128, 1>;
+    }
+    switch (p.K) {
+        case 1: return kraskov_direct_kernel<1, 8, SYM>;
+        case 2: return kraskov_direct_kernel<2, 8, SYM>;
+        case 3: return kraskov_direct_kernel<3, 8, SYM>;
+        case 4: return kraskov_direct_kernel<4, 8, SYM>;
+        case 8: return kraskov_direct_kernel<8, 4, SYM>;
+        case 16: return kraskov_direct_kernel<16, 2, SYM>;
+        case 32: return kraskov_direct_kernel<32, 1, SYM>;
+        default: return kraskov_direct_kernel<64, 1, SYM>;
+    }
+}
+
+DirectKernel direct_kernel(const KraskovPlan& p) {
+    if (!p.dxt) return direct_plain_kernel<false>(p);
+    switch (p.K) {
+        case 1: return direct_table_kernel_k<1>(p);
+        case 2: return direct_table_kernel_k<2>(p);
+        case 3: return direct_table_kernel_k<3>(p);
+        default: return direct_table_kernel_k<4>(p);
+    }
+}
+
+struct KraskovTables {
+    const double *psi, *noise_ref, *noise_query;
+};
+KraskovTables kraskov_tables(const double* d_tables, int cs) {
     const double* noise_ref = d_tables + 2 * (cs + 1);
-    const double* noise_query = noise_ref + cs;
+    return {d_tables, noise_ref, noise_ref + cs};
+}
+
+KraskovSwitches read_switches() {  // at every call: the tests set them after the library is loaded
+    auto first_char = [](const char* name) {
+        const char* e = getenv(name);
+        return !e ? -1 : *e == '0' ? 0 : *e == '1' ? 1 : 2;
+    };
+    return {first_char("CRF_KRASKOV_SORTED"), first_char("CRF_KRASKOV_DIRECT"), first_char("CRF_KRASKOV_TILE"),
+            first_char("CRF_KRASKOV_DXT"),    first_char("CRF_KRASKOV_TI4"),    first_char("CRF_KRASKOV_STAGE")};
+}
+
+// kraskov_direct_kernel: 256 lanes; one block per group of four voxel tiles up to 65536 blocks (r01 capped the grid at
+// 4096: with ~768 blocks resident that is 5.3 rounds of equally long blocks, the last round a third full).  The host
+// always passes share = 1 (the four waves of a block share a voxel tile); the kernel's share == 0 branches are left in
+// because taking them out changes its ISA -- a later change with its own measurement.
+template <class... Args>
+void launch_direct(DirectKernel kernel, const KraskovPlan& p, size_t num_voxels, int cs, hipStream_t s, Args... args) {
+    const size_t groups = ((num_voxels + 63) / 64 + 3) / 4;
+    const size_t lds = kraskov_table_bytes(cs) + (p.stage ? kraskov_stage_bytes(cs) : 0);
+    hipLaunchKernelGGL(kernel, dim3(unsigned(groups < 65536 ? groups : 65536)), dim3(256), lds, s, args..., 1);
+}
+
+// The reference side if asked for, then the planned kernel between the two events.
+hipError_t launch_field(const KraskovPlan& p, const float* const* d_members, int cs, size_t num_voxels,
+                        const RefSource& ref, const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out,
+                        hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    const KraskovTables t = kraskov_tables(d_tables, cs);
     double* prep = reinterpret_cast<double*>(d_prep);
-    if (ref.prepare()) launch_kraskov_prep(ref, d_members, cs, noise_ref, prep, s);
+    if (ref.prepare()) launch_kraskov_prep(ref, d_members, cs, t.noise_ref, prep, s);
     if (!ref.run()) return hipGetLastError();
     const size_t tiles = (num_voxels + 63) / 64;
-    const size_t groups = (tiles + 3) / 4;
-    // one block per group of four voxel tiles up to 65536 blocks (r01 capped the grid at 4096: with ~768 blocks resident
-    // that is 5.3 rounds of equally long blocks, the last round a third full)
-    const char* cap_env = getenv("CRF_KRASKOV_GRID");  // tuning
-    const size_t cap = cap_env && atoi(cap_env) > 0 ? size_t(atoi(cap_env)) : 65536;
-    const unsigned blocks = unsigned(groups < cap ? groups : cap);
-    const int share = direct_share_tiles();
-    // The tile staged in LDS (table kernels, 4 points per sweep): every member value is fetched ONCE.  Up to 64 members the
-    // 16 KB tile costs no occupancy -- 256^3: 64 members k = 3 / 4 26.3 / 29.7 ms against 26.2 / 31.6 ms, 32 members 7.0
-    // against 7.3 -- beyond that it does (80 / 100 members k = 3: 46.4 / 80.0 against 40.2 / 64.6 ms); k = 1, 2 keep their
-    // 8-point sweeps (64 members k = 2: 23.2 ms staged with 4 points against 21.6).  CRF_KRASKOV_STAGE=0/1 overrides.
-    const char* stage_env = getenv("CRF_KRASKOV_STAGE");
-    const bool stage_fits = lds + size_t(cs) * 256 + kDirectSumBytes <= 64 * 1024;
-    const bool stage = share && stage_fits && (stage_env ? *stage_env == '1' : (cs <= 64 && kk >= 3));
-    const size_t lds_stage = lds + size_t(cs) * 256;
     if (ev_begin) (void)hipEventRecord(ev_begin, s);
-#define CRF_LAUNCH_DIRECT(K, TI)                                                                                    \
-    hipLaunchKernelGGL((kraskov_direct_kernel<K, TI>), dim3(blocks), dim3(256), lds, s, d_members, nullptr, prep, psi, \
-                       noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term, share)
-    // K = k exactly for the small k (the sorted insertion costs 2K - 1 min/max per candidate: K = 4 for k = 3 is 7
-    // instead of 5; measured at 256^3 x 64, k = 3: <3, 8> 36.2 ms vs <4, 8> 48.6 ms)
-    // up to 128 members the x distances can come from the prepared table (scalar loads)
-    const char* dxt_env = getenv("CRF_KRASKOV_DXT");  // tuning: 0 = compute them per pair
-    // (the table outgrows the 16 KB scalar cache early but keeps paying up to 112 members -- 256^3: 100 members k = 3 / 4
-    // 67.8 / 79.5 vs 76.2 / 87.7 ms -- and for k = 2, 4 up to 128: 81.6 / 122.5 vs 85.6 / 129.9 ms; k = 1, 3 at 128: 74.5 /
-    // 109.9 vs 73.3 / 107.6 ms)
-    const bool table_pays = cs <= 112 || kk == 2 || kk == 4;
-    const bool use_dxt = cs <= kDxtMaxMembers && ((dxt_env && *dxt_env == '1') || (table_pays && !(dxt_env && *dxt_env == '0')));
-#define CRF_LAUNCH_DIRECT_DXT_TI(K, TI)                                                                                  \
-    hipLaunchKernelGGL((kraskov_direct_kernel<K, TI, false, true>), dim3(blocks), dim3(256), lds, s, d_members, nullptr, \
-                       prep, psi, noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term, share)
-#define CRF_LAUNCH_DIRECT_DXT(K) CRF_LAUNCH_DIRECT_DXT_TI(K, 8)
-#define CRF_LAUNCH_STAGED(K)                                                                                              \
-    hipLaunchKernelGGL((kraskov_direct_kernel<K, 4, false, true, true>), dim3(blocks), dim3(256), lds_stage, s, d_members, \
-                       nullptr, prep, psi, noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term, share)
-    // 4 points per sweep instead of 8 for K = 3 and 4: half the registers (94 / 119 instead of 156 / 188: 5 / 4 waves per
-    // SIMD instead of 3 / 2) and one s_load_dwordx8 per candidate row -- 256^3 with the table: k = 4 at 32 / 48 / 64 / 80
-    // members 8.7 / 17.5 / 30.5 / 46.4 ms against 10.6 / 21.6 / 37.9 / 57.7 ms, k = 3 at 48 / 64 / 80: 14.8 / 25.8 / 39.3
-    // against 15.4 / 27.0 / 41.7 ms; K = 1, 2 lose (64 members: 20.6 / 23.0 vs 18.0 / 21.1 ms).  Without the table
-    // (beyond 80 members) K = 4 gains (128 members 129 vs 149 ms), K = 3 loses (117 vs 108 ms).  2 points per sweep
-    // (77-79 registers, 6 waves) lose again: 64 members k = 3 / 4 31.5 / 34.8 ms.
-    const char* ti4_env = getenv("CRF_KRASKOV_TI4");  // tuning: 1 = 4 points per sweep for every K <= 4, 0 = 8
-    const bool ti4_table = ti4_env ? *ti4_env == '1' : kk >= 3;
-    const bool ti4_k4 = ti4_env ? *ti4_env == '1' : true;
-    const bool ti4_k3_plain = ti4_env && *ti4_env == '1';
-    const bool ti4 = ti4_table;
-    if (use_dxt && kk <= 4 && stage) {
-        switch (kk) {
-            case 1: CRF_LAUNCH_STAGED(1); break;
-            case 2: CRF_LAUNCH_STAGED(2); break;
-            case 3: CRF_LAUNCH_STAGED(3); break;
-            default: CRF_LAUNCH_STAGED(4); break;
+    switch (p.family) {
+        case KraskovFamily::Direct:
+            launch_direct(direct_kernel(p), p, num_voxels, cs, s, d_members, static_cast<const float* const*>(nullptr), prep,
+                          t.psi, t.noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term);
+            break;
+        case KraskovFamily::Sorted:  // two waves per block, a tile per block and round
+            hipLaunchKernelGGL(sorted_kernel(p), dim3(unsigned(tiles < 65536 ? tiles : 65536)), dim3(128),
+                               kraskov_table_bytes(cs), s, d_members, prep, t.psi, t.noise_query, d_out, num_voxels, cs, a.k,
+                               a.estimator, int(a.to_cc), a.c_term);
+            break;
+        case KraskovFamily::Column: {  // one wave per tile: four tables (psi padded to 16 bytes) and the cs x 64 column
+            const size_t lds = size_t(4 * cs + 1 + ((cs + 1) & 1)) * sizeof(double) + size_t(cs) * 64 * sizeof(float);
+            hipLaunchKernelGGL(column_kernel(p), dim3(unsigned(tiles)), dim3(64), lds, s, d_members, prep, t.psi,
+                               t.noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term);
+            break;
         }
-    } else if (use_dxt && kk <= 4) {
-        switch (kk) {
-            case 1:
-                if (ti4) {
-                    CRF_LAUNCH_DIRECT_DXT_TI(1, 4);
-                } else {
-                    CRF_LAUNCH_DIRECT_DXT(1);
-                }
-                break;
-            case 2:
-                if (ti4) {
-                    CRF_LAUNCH_DIRECT_DXT_TI(2, 4);
-                } else {
-                    CRF_LAUNCH_DIRECT_DXT(2);
-                }
-                break;
-            case 3:
-                if (ti4) {
-                    CRF_LAUNCH_DIRECT_DXT_TI(3, 4);
-                } else {
-                    CRF_LAUNCH_DIRECT_DXT(3);
-                }
-                break;
-            default:
-                if (ti4) {
-                    CRF_LAUNCH_DIRECT_DXT_TI(4, 4);
-                } else {
-                    CRF_LAUNCH_DIRECT_DXT(4);
-                }
-                break;
-        }
-    } else if (kk == 1) {
-        CRF_LAUNCH_DIRECT(1, 8);
-    } else if (kk == 2) {
-        CRF_LAUNCH_DIRECT(2, 8);
-    } else if (kk == 3) {
-        if (ti4_k3_plain) {
-            CRF_LAUNCH_DIRECT(3, 4);
-        } else {
-            CRF_LAUNCH_DIRECT(3, 8);
-        }
-    } else if (kk <= 4) {
-        if (ti4_k4) {
-            CRF_LAUNCH_DIRECT(4, 4);
-        } else {
-            CRF_LAUNCH_DIRECT(4, 8);
-        }
-    } else if (kk <= 8) {
-        CRF_LAUNCH_DIRECT(8, 4);
-    } else if (kk <= 16) {
-        CRF_LAUNCH_DIRECT(16, 2);
-    } else if (kk <= 32) {
-        CRF_LAUNCH_DIRECT(32, 1);
-    } else if (kk <= 64) {
-        CRF_LAUNCH_DIRECT(64, 1);
-    } else {
-        CRF_LAUNCH_DIRECT(128, 1);
     }
-#undef CRF_LAUNCH_DIRECT
-#undef CRF_LAUNCH_DIRECT_DXT
-#undef CRF_LAUNCH_DIRECT_DXT_TI
     if (ev_end) (void)hipEventRecord(ev_end, s);
-    if (info) info->kernel_name = "kraskov_direct_kernel";
+    if (info)
+        info->kernel_name = p.family == KraskovFamily::Direct   ? "kraskov_direct_kernel"
+                            : p.family == KraskovFamily::Sorted ? "kraskov_sorted_kernel"
+                                                                : "mi_kraskov_kernel";
     return hipGetLastError();
 }
 
-// sorted-column kernel: cs <= 64, k <= 4
-hipError_t launch_mi_kraskov_sorted(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
+}  // namespace
+
+// 2..128 members: whichever kernel kraskov_field_plan picks
+hipError_t launch_mi_kraskov(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
+                             const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
+                             hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    if (cs == 1) return launch_single_member(ref, d_out, num_voxels, s, ev_begin, ev_end, info);
+    KraskovPlan plan;
+    if (!kraskov_field_plan(cs, a.k, false, read_switches(), &plan)) return hipErrorNotSupported;
+    return launch_field(plan, d_members, cs, num_voxels, ref, a, d_tables, d_prep, d_out, s, ev_begin, ev_end, info);
+}
+
+// any cs (tables must fit LDS: cs <= 2048), k <= 128; hipErrorNotSupported otherwise
+hipError_t launch_mi_kraskov_direct(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                                     const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out,
                                     hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
-    const int kk = a.k < cs - 1 ? a.k : cs - 1;
-    if (kk > 4 || kk < 1 || cs > 64) return hipErrorNotSupported;
-    const size_t lds = size_t(3 * cs) * sizeof(double);
-    const double* psi = d_tables;
-    const double* noise_ref = d_tables + 2 * (cs + 1);
-    const double* noise_query = noise_ref + cs;
-    double* prep = reinterpret_cast<double*>(d_prep);
-    if (ref.prepare()) launch_kraskov_prep(ref, d_members, cs, noise_ref, prep, s);
-    if (!ref.run()) return hipGetLastError();
-    const size_t tiles = (num_voxels + 63) / 64;
-    const unsigned blocks = unsigned(tiles < 65536 ? tiles : 65536);
-    if (ev_begin) (void)hipEventRecord(ev_begin, s);
-#define CRF_LAUNCH_SORTED(K, NS)                                                                                     \
-    hipLaunchKernelGGL((kraskov_sorted_kernel<K, NS, 2>), dim3(blocks), dim3(128), lds, s, d_members, prep, psi,      \
-                       noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term)
-#define CRF_LAUNCH_SORTED_K(NS)                   \
-    switch (kk) {                                 \
-        case 1: CRF_LAUNCH_SORTED(1, NS); break;  \
-        case 2: CRF_LAUNCH_SORTED(2, NS); break;  \
-        case 3: CRF_LAUNCH_SORTED(3, NS); break;  \
-        default: CRF_LAUNCH_SORTED(4, NS); break; \
-    }
-    if (cs <= 32) {
-        CRF_LAUNCH_SORTED_K(32)
-    } else if (cs <= 48) {
-        CRF_LAUNCH_SORTED_K(48)
-    } else {
-        CRF_LAUNCH_SORTED_K(64)
-    }
-#undef CRF_LAUNCH_SORTED_K
-#undef CRF_LAUNCH_SORTED
-    if (ev_end) (void)hipEventRecord(ev_end, s);
-    if (info) info->kernel_name = "kraskov_sorted_kernel";
-    return hipGetLastError();
+    KraskovPlan plan;
+    if (!kraskov_field_plan(cs, a.k, true, read_switches(), &plan)) return hipErrorNotSupported;
+    return launch_field(plan, d_members, cs, num_voxels, ref, a, d_tables, d_prep, d_out, s, ev_begin, ev_end, info);
 }
 
 // symmetric field mode: X = d_members_x (reference field), Y = d_members_y (query field); KSG-1
@@ -1068,126 +1015,11 @@ hipError_t launch_mi_kraskov_symmetric(const float* const* d_members_x, const fl
                                        size_t num_voxels, int k, double c_term, bool to_cc, const double* d_tables,
                                        float* d_out, hipStream_t s) {
     if (cs == 1) return launch_fill(d_out, num_voxels, 1.0f, s);
-    const int kk = k < cs - 1 ? k : cs - 1;
-    const size_t lds = size_t(3 * cs) * sizeof(double);
-    if (kk > 64 || lds + kDirectSumBytes > 60 * 1024) return hipErrorNotSupported;
-    const double* psi = d_tables;
-    const double* noise_ref = d_tables + 2 * (cs + 1);
-    const double* noise_query = noise_ref + cs;
-    const size_t tiles = (num_voxels + 63) / 64;
-    const size_t groups = (tiles + 3) / 4;
-    const unsigned blocks = unsigned(groups < 65536 ? groups : 65536);
-    const int share = direct_share_tiles();
-#define CRF_LAUNCH_SYM(K, TI)                                                                                        \
-    hipLaunchKernelGGL((kraskov_direct_kernel<K, TI, true>), dim3(blocks), dim3(256), lds, s, d_members_y, d_members_x, \
-                       noise_ref, psi, noise_query, d_out, num_voxels, cs, k, 1, int(to_cc), c_term, share)
-    if (kk == 1) {
-        CRF_LAUNCH_SYM(1, 8);
-    } else if (kk == 2) {
-        CRF_LAUNCH_SYM(2, 8);
-    } else if (kk == 3) {
-        CRF_LAUNCH_SYM(3, 8);
-    } else if (kk <= 4) {
-        CRF_LAUNCH_SYM(4, 8);
-    } else if (kk <= 8) {
-        CRF_LAUNCH_SYM(8, 4);
-    } else if (kk <= 16) {
-        CRF_LAUNCH_SYM(16, 2);
-    } else if (kk <= 32) {
-        CRF_LAUNCH_SYM(32, 1);
-    } else {
-        CRF_LAUNCH_SYM(64, 1);
-    }
-#undef CRF_LAUNCH_SYM
-    return hipGetLastError();
-}
-
-hipError_t launch_mi_kraskov(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
-                             const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
-                             hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
-    if (cs == 1) {
-        if (!ref.run()) return hipSuccess;
-        if (ev_begin) (void)hipEventRecord(ev_begin, s);
-        hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
-        if (ev_end) (void)hipEventRecord(ev_end, s);
-        if (info) info->kernel_name = "fill_kernel";
-        return e;
-    }
-    const int kk = a.k < cs - 1 ? a.k : cs - 1;
-    const char* force_direct = getenv("CRF_KRASKOV_DIRECT");  // tuning: the tile-free kernel for every k
-    // The LDS-tile kernels below are instantiated for k <= 4 and hold a 256*cs-byte column per wave, which caps the
-    // occupancy beyond ~80 members (measured at 256^3, k = 3: 80 members 71 vs 72 ms, 96: 112 vs 100 ms, 128: 226 vs
-    // 171 ms, tile vs tile-free): the tile-free kernel takes over there and for every larger k.
-    // r02 dispatch (256^3, profiles/r02_kraskov_tile_vs_direct.txt, profiles/tuning_r02.md).  Small member counts: the
-    // LDS-column kernel with 8 points per sweep (three to four waves per SIMD, no batch padding): k = 3 at 32 / 40
-    // members 7.2 / 11.5 ms vs 7.2 / 12.4 ms tile-free.  Beyond that the tile-free kernel with the scalar-loaded
-    // x-distance table, 8 points per sweep for k = 1, 2 and 4 for k = 3, 4 (k = 3: 48 / 56 / 64 / 80 members 14.8 / 22.2 /
-    // 25.8 / 39.3 ms; k = 4: 32 / 48 / 64 / 80 members 8.5 / 17.5 / 30.5 / 46.4 ms, LDS column 9.5 / 21.7 / - / -) -- its
-    // four waves share a voxel tile, so its re-reads stay in L1 / L2 (see the kernel).  The sorted-column kernel (k = 4
-    // at 64 members: 34.9 ms) is no longer the fastest anywhere and runs only when asked for (CRF_KRASKOV_SORTED=1).
-    const char* sorted = getenv("CRF_KRASKOV_SORTED");  // tuning: 1 = wherever it exists, 0 = never
-    if (kk <= 4 && cs <= 64 && !(sorted && *sorted == '0') && !(force_direct && *force_direct == '1') &&
-        (sorted && *sorted == '1')) {
-        hipError_t e = launch_mi_kraskov_sorted(d_members, cs, num_voxels, ref, a, d_tables, d_prep, d_out, s, ev_begin,
-                                                ev_end, info);
-        if (e != hipErrorNotSupported) return e;
-    }
-    const char* force_tile = getenv("CRF_KRASKOV_TILE");  // tuning: the LDS-column kernel wherever it exists
-    const bool prefer_direct = kk <= 2 ? cs > 44 : (kk == 3 ? cs > 40 : (cs > 36 || (cs > 28 && cs <= 32)));
-    if (kk > 4 || cs > 80 || (force_direct && *force_direct == '1') ||
-        (prefer_direct && !(force_tile && *force_tile == '1'))) {
-        hipError_t e = launch_mi_kraskov_direct(d_members, cs, num_voxels, ref, a, d_tables, d_prep, d_out, s, ev_begin,
-                                                ev_end, info);
-        if (e != hipErrorNotSupported) return e;
-    }
-    const double* psi = d_tables;
-    const double* noise_ref = d_tables + 2 * (cs + 1);
-    const double* noise_query = noise_ref + cs;
-    double* prep = reinterpret_cast<double*>(d_prep);
-    if (ref.prepare()) launch_kraskov_prep(ref, d_members, cs, noise_ref, prep, s);
-    if (!ref.run()) return hipGetLastError();
-    const unsigned blocks = unsigned((num_voxels + 63) / 64);
-    size_t lds = size_t(4 * cs + 1 + ((cs + 1) & 1)) * sizeof(double) + size_t(cs) * 64 * sizeof(float);
-    if (const char* pad = getenv("CRF_KRASKOV_LDS_PAD")) lds += size_t(atoi(pad));  // tuning: occupancy experiments
-    if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    // 16 points per sweep only where the column caps the occupancy at two waves per SIMD anyway (more than 56 members)
-    const char* narrow = getenv("CRF_KRASKOV_TI8");  // tuning: 8 points per sweep for every member count
-    const bool wide = cs > 56 && (cs % 16 == 0 || cs % 16 > 8) && !(narrow && *narrow == '1');
-    // the distance table pays here while it fits the 16 KB scalar cache (256^3, k = 3: 32 members 7.2 vs 8.1 ms; 40
-    // members 12.0 vs 11.6 ms; 48 members 17.3 vs 16.4 ms)
-    const char* dxt_env = getenv("CRF_KRASKOV_DXT");  // tuning: 0 = x distances computed per pair, 1 = table up to 80
-    const bool use_dxt = (dxt_env && *dxt_env == '1') ? cs <= kDxtMaxMembers : (cs <= 32 && !(dxt_env && *dxt_env == '0'));
-#define CRF_LAUNCH_KRASKOV(K, TI)                                                                                        \
-    if (use_dxt && K > 0 && TI <= 8)                                                                                     \
-        hipLaunchKernelGGL((mi_kraskov_kernel<K, TI, (K > 0 && TI <= 8)>), dim3(blocks), dim3(64), lds, s, d_members,    \
-                           prep, psi, noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term);     \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((mi_kraskov_kernel<K, TI>), dim3(blocks), dim3(64), lds, s, d_members, prep, psi,            \
-                           noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term)
-    switch (kk) {
-        case 1: CRF_LAUNCH_KRASKOV(1, 8); break;
-        // 16 points per sweep where the member count fills the last tile well: 253 VGPRs still give the 2 waves per SIMD
-        // that the LDS column allows anyway (256^3 x 64, k = 3: 37.4 ms vs 39.7 ms at 8 points, 45.3 ms at 4)
-        case 2:
-            if (wide) {
-                CRF_LAUNCH_KRASKOV(2, 16);
-            } else {
-                CRF_LAUNCH_KRASKOV(2, 8);
-            }
-            break;
-        case 3:
-            if (wide) {
-                CRF_LAUNCH_KRASKOV(3, 16);
-            } else {
-                CRF_LAUNCH_KRASKOV(3, 8);
-            }
-            break;
-        case 4: CRF_LAUNCH_KRASKOV(4, 4); break;
-        default: CRF_LAUNCH_KRASKOV(0, 1); break;
-    }
-#undef CRF_LAUNCH_KRASKOV
-    if (ev_end) (void)hipEventRecord(ev_end, s);
-    if (info) info->kernel_name = "mi_kraskov_kernel";
+    KraskovPlan plan;
+    if (!kraskov_symmetric_plan(cs, k, &plan)) return hipErrorNotSupported;
+    const KraskovTables t = kraskov_tables(d_tables, cs);
+    launch_direct(direct_plain_kernel<true>(plan), plan, num_voxels, cs, s, d_members_y, d_members_x, t.noise_ref, t.psi,
+                  t.noise_query, d_out, num_voxels, cs, k, 1, int(to_cc), c_term);
     return hipGetLastError();
 }
 

@@ -1515,17 +1515,6 @@ hipError_t launch_plan(const RankPlan<P>& plan, const float* const* d_members, c
     return hipGetLastError();
 }
 
-// One member: every rank vector is (1), the coefficient is 1 by the reference's convention.
-hipError_t launch_single_member(const RefSource& ref, float* d_out, size_t num_voxels, hipStream_t s,
-                                hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
-    if (!ref.run()) return hipSuccess;
-    if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    hipError_t e = launch_fill(d_out, num_voxels, 1.0f, s);
-    if (ev_end) (void)hipEventRecord(ev_end, s);
-    if (info) info->kernel_name = "fill_kernel";
-    return e;
-}
-
 int pad_pow2(int cs) { return cs <= 8 ? 8 : cs <= 16 ? 16 : cs <= 32 ? 32 : cs <= 64 ? 64 : 128; }
 
 }  // namespace

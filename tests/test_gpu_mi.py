@@ -197,6 +197,22 @@ def test_kraskov_distance_table_boundary(engine, oracle, monkeypatch, cs, dxt):
     assert engine.last_kernel_name() == "kraskov_direct_kernel"
 
 
+@pytest.mark.parametrize("k,cs,expected", [
+    (3, 40, "mi_kraskov_kernel"), (3, 41, "kraskov_direct_kernel"),
+    (2, 44, "mi_kraskov_kernel"), (2, 45, "kraskov_direct_kernel"),
+    (4, 28, "mi_kraskov_kernel"), (4, 29, "kraskov_direct_kernel"),
+    (4, 32, "kraskov_direct_kernel"), (4, 33, "mi_kraskov_kernel"),
+    (4, 36, "mi_kraskov_kernel"), (4, 37, "kraskov_direct_kernel"),
+    (5, 20, "kraskov_direct_kernel")])
+def test_kraskov_default_dispatch_boundaries(engine, oracle, k, cs, expected):
+    """No switch set: both sides of every member count at which the default dispatch changes from the LDS-column kernel
+    to the tile-free one or back, and k beyond 4, which only the tile-free kernel has."""
+    ens = synth.normal_ensemble(16, 6, 4, cs, seed=11 * cs + k)
+    _check(engine, oracle, ens, Measure.MUTUAL_INFORMATION_KRASKOV, oracle_lib.MI_KRASKOV, f"KSG-1 cs={cs} k={k}",
+           ref_xyz=(7, 3, 2), k=k, min_identical=0.99)
+    assert engine.last_kernel_name() == expected
+
+
 @pytest.mark.parametrize("cs,k", [(16, 2), (64, 3), (100, 5), (64, 12), (100, 40), (160, 70)])
 def test_kraskov_ksg2(engine, oracle, cs, k):
     ens = synth.normal_ensemble(16, 8, 6, cs, seed=400 + cs)
