@@ -27,19 +27,30 @@
  *   Pearson / Spearman / Kendall: PINNED.  oracle/Makefile compiles the reference's own Correlation.cpp into
  *     oracle/_ref/libref_corr.so and tests/test_oracle_vs_ref.py + oracle/make_golden.py check this file
  *     bit-for-bit against it; the reference outputs are committed under tests/golden/.
- *   binned MI / Kraskov MI: PARITY UNPINNED against reference object code.  MutualInformation.cpp needs
- *     boost::math::digamma, sgl::KdTreed, sgl::XorshiftRandomGenerator and glm, none of which are in
- *     /root/reference or this image, and the reference holds no tests/golden vectors for the path.  These two
- *     estimators are a restatement of the published algorithm anchored on the reference's call sites:
- *       - boost::math::digamma is only ever evaluated at positive integers (MutualInformation.cpp:235,237,
- *         438,439,503,504): psi(n) = -gamma + H_{n-1}, tabulated here in long double.
- *       - sgl::KdTreed<double,2,CHEBYSHEV>::findKNearestNeighbors is an exact k-NN search
- *         (MutualInformation.cpp:426-434): any exact search yields the same distances; brute force here.
+ *   binned MI / Kraskov MI / MI-CC / DKL: PINNED IN PART.  MutualInformation.cpp and DKL.cpp need boost::math::digamma,
+ *     sgl::KdTreed, sgl::XorshiftRandomGenerator, sgl's Math.hpp and glm, none of which is available.  oracle/Makefile
+ *     compiles the two files unmodified, where they lie, over the stand-in headers of oracle/standins/ into
+ *     oracle/_ref/libref_mi.so (driver: oracle/ref_mi_driver.cpp), and tests/test_oracle_vs_ref_mi.py holds this file
+ *     bit-identical to that object code; the MI / DKL golden vectors are its outputs.
+ *       - pinned bit-identically: the reference's own arithmetic in the two files (bin indices and the compiled int() of
+ *         an overflowing one, normalisation and summation order, epsilon thresholds, the `<` of the range counts, how
+ *         the noise is applied, the DKL window descent, clamps and casts);
+ *       - stand-ins (this repository's code, tested by themselves): boost::math::digamma, which the reference only
+ *         evaluates at integers (MutualInformation.cpp:235,237,438,439,503,504): psi(n) = -gamma + H_{n-1} in long
+ *         double, a pole at 0 (boost throws, NaN here); sgl::KdTreed<double,2,CHEBYSHEV>::findKNearestNeighbors, an
+ *         exact k-NN search (MutualInformation.cpp:426-434): any exact search yields the same distances, brute force
+ *         here and there; sgl's PI / TWO_PI (float) / sqr / iceil;
+ *       - assumed: the neighbour query REPLACES the contents of its output vectors.  computeMutualInformationKraskov2
+ *         clears the distance vector per point but never the neighbour vector (MutualInformation.cpp:485-488) and takes
+ *         maxima over all of it; a query that appended would make KSG-2 collapse to 0 everywhere.  sgl's source is not
+ *         available; this file, the kernels and the stand-in all assume "replaces";
  *       - sgl::XorshiftRandomGenerator (github.com/chrismile/sgl, cloned unpinned at HEAD by build.sh:1039-1043)
  *         is NOT available: the 1e-10 tie-breaking noise stream is this repo's own documented xorshift32
- *         stream (see noise01()).  On tie-free data the noise cannot change any neighbour count, so results
- *         are independent of the stream; on exact ties they are stream-dependent (documented in DESIGN.md).
- *     They are cross-checked in tests/ against independent numpy/scipy formulations and analytic values.
+ *         stream (see noise01()), in the stand-in too.  On tie-free data the noise cannot change any neighbour count,
+ *         so results are independent of the stream; on exact ties they are stream-dependent;
+ *       - not pinned: the calculator level (per-voxel loops, NaN and cs == 1 rules, binned normalisation, MI-CC map)
+ *         of CorrelationCalculator.cpp / DKLCalculator.cpp / HEBChartCorrelation.cpp, restated here and in the driver.
+ *     They are also cross-checked in tests/ against independent numpy/scipy formulations and analytic values.
  *
  * Build: see oracle/Makefile (g++ -std=c++17 -O2 -ffp-contract=off -fopenmp; no -march, no fast-math, mirroring
  * the reference's CMakeLists.txt:13,34-36 so fp32 semantics are those of the reference build).
@@ -364,9 +375,10 @@ inline float mi_to_cc(float mi) {  // CorrelationCalculator.cpp:1071-1073,1130-1
 // ---------------------------------------------------------------------------------------------------------------
 // DKLCalculator: Kullback-Leibler divergence between a voxel's normalised ensemble distribution and N(0,1)
 // (src/Calculators/DKL.cpp:38-165, driver src/Calculators/DKLCalculator.cpp:134-262, Real = double).  DKL.cpp needs
-// boost::math::digamma and sgl's Math.hpp (PI, TWO_PI, sqr, iceil) and cannot be compiled here: restated.  PARITY
-// UNPINNED for the two sgl constants: sgl declares PI / TWO_PI as `float` (so `std::log(sgl::TWO_PI)` is the float
-// overload); should a build use double constants the results move by < 1e-7 absolute, inside the stated tolerance.
+// boost::math::digamma and sgl's Math.hpp (PI, TWO_PI, sqr, iceil): restated, and held bit-identical to DKL.cpp compiled
+// over oracle/standins/ (tests/test_oracle_vs_ref_mi.py).  The two sgl constants are the stand-in's: sgl declares PI /
+// TWO_PI as `float` (so `std::log(sgl::TWO_PI)` is the float overload); should a build use double constants the results
+// move by < 1e-7 absolute, inside the stated tolerance.
 // ---------------------------------------------------------------------------------------------------------------
 static const float SGL_PI = 3.1415926535897932f;
 static const float SGL_TWO_PI = SGL_PI * 2.0f;

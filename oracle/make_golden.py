@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.npz -- small input/output vectors for the correlation-field path.
 
-Run in the BUILD container only (needs oracle/_ref/libref_corr.so, i.e. /root/reference):  python oracle/make_golden.py
+Run in the BUILD container only (needs oracle/_ref/, i.e. /root/reference):  python oracle/make_golden.py
   * Pearson / Spearman / Kendall expected outputs come from the REFERENCE's own object code
     (src/Calculators/Correlation.cpp compiled where it lies, driven by oracle/ref_driver.cpp).
-  * binned / Kraskov MI expected outputs come from this repo's CPU restatement (oracle/corr_oracle.cpp): the
-    reference's MutualInformation.cpp cannot be built here (boost, sgl, glm absent) -- those files are labelled
-    "restatement" and pin the restatement against regressions, not against the reference ("parity unpinned").
+  * binned / Kraskov MI and DKL expected outputs come from the REFERENCE's own object code too
+    (MutualInformation.cpp and DKL.cpp compiled where they lie over oracle/standins/, driven by
+    oracle/ref_mi_driver.cpp) and are labelled "reference": what is the reference's there is the arithmetic of those
+    two files; digamma, the k-NN search and the noise stream are stand-ins, the field loops are driver code.
+  * ensemble mean / spread, set predicates and the tiled layout stay "restatement" (regression pins of the oracle).
 Inputs are regenerated from seeds by this script; the arrays are stored so that the fixtures are self-contained data.
 """
 import sys
@@ -47,7 +49,7 @@ def case_inputs():
 
 def main():
     if not oracle_lib.reference_available():
-        raise SystemExit("oracle/_ref/libref_corr.so missing: run `make -C oracle` where /root/reference exists")
+        raise SystemExit("oracle/_ref/ libraries missing: run `make -C oracle` where /root/reference exists")
     ref = oracle_lib.load_reference()
     oracle = oracle_lib.load_oracle()
     OUT.mkdir(parents=True, exist_ok=True)
@@ -60,29 +62,28 @@ def main():
         data["pearson__reference"] = ref.field(0, ens, refv)
         data["spearman__reference"] = ref.field(1, ens, refv)
         data["kendall__reference"] = ref.field(2, ens, refv)
-        data["mi_binned__restatement"] = oracle.field(oracle_lib.MI_BINNED, ens, refv, num_bins=80, minmax_ref=(mn, mx))
-        data["binned_mi_cc__restatement"] = oracle.field(oracle_lib.BINNED_MI_CC, ens, refv, num_bins=80,
-                                                         minmax_ref=(mn, mx))
-        data["mi_kraskov__restatement"] = oracle.field(oracle_lib.MI_KRASKOV, ens, refv, k=k)
-        data["mi_kraskov_k3__restatement"] = oracle.field(oracle_lib.MI_KRASKOV, ens, refv, k=min(3, max(cs - 1, 1)))
-        data["mi_kraskov2__restatement"] = oracle.field(oracle_lib.MI_KRASKOV, ens, refv, k=k, estimator=2)
-        data["kmi_cc__restatement"] = oracle.field(oracle_lib.KMI_CC, ens, refv, k=k)
+        data["mi_binned__reference"] = ref.mi_field(oracle_lib.MI_BINNED, ens, refv, num_bins=80, minmax_ref=(mn, mx))
+        data["binned_mi_cc__reference"] = ref.mi_field(oracle_lib.BINNED_MI_CC, ens, refv, num_bins=80,
+                                                       minmax_ref=(mn, mx))
+        data["mi_kraskov__reference"] = ref.mi_field(oracle_lib.MI_KRASKOV, ens, refv, k=k)
+        data["mi_kraskov_k3__reference"] = ref.mi_field(oracle_lib.MI_KRASKOV, ens, refv, k=min(3, max(cs - 1, 1)))
+        data["mi_kraskov2__reference"] = ref.mi_field(oracle_lib.MI_KRASKOV, ens, refv, k=k, estimator=2)
+        data["kmi_cc__reference"] = ref.mi_field(oracle_lib.KMI_CC, ens, refv, k=k)
         np.savez_compressed(OUT / f"{name}.npz", **data)
         print(f"{name}: cs={cs} voxels={ens[0].size} -> {(OUT / (name + '.npz')).stat().st_size} bytes")
-    # pair-request path (HEBChartCorrelation.cpp:493-600): reference primitives for Pearson/Spearman/Kendall,
-    # restatement for the MI estimators
+    # pair-request path (HEBChartCorrelation.cpp:493-600): the reference's primitives for every measure
     from test_pair_requests import _case
     ens, pairs, ii, jj = _case(32, 4242, n=300)
     np.savez_compressed(
         OUT / "pair_requests.npz", members=ens, pairs=pairs, idx_i=ii, idx_j=jj,
         pearson__reference=ref.pair_requests(0, ens, ii, jj), spearman__reference=ref.pair_requests(1, ens, ii, jj),
         kendall__reference=ref.pair_requests(2, ens, ii, jj),
-        mi_binned__restatement=oracle.pair_requests(3, ens, ii, jj, num_bins=80),
-        mi_kraskov__restatement=oracle.pair_requests(4, ens, ii, jj, k=3))
+        mi_binned__reference=ref.mi_pair_requests(3, ens, ii, jj, num_bins=80),
+        mi_kraskov__reference=ref.mi_pair_requests(4, ens, ii, jj, k=3))
     print("pair_requests: 300 requests, cs=32")
     # two-field modes and sibling reductions.  Symmetric Pearson/Spearman/Kendall expectations
-    # come from the reference's primitives applied voxel by voxel to (field 1, field 2); everything else from the
-    # restatement (regression pins).
+    # come from the reference's primitives applied voxel by voxel to (field 1, field 2), the MI and DKL ones from the
+    # reference's estimators behind oracle/ref_mi_driver.cpp; the rest from the restatement (regression pins).
     rng = np.random.default_rng(4711)
     fa = rng.standard_normal((24, 4, 6, 8)).astype(np.float32)
     fb = (0.6 * fa + 0.8 * rng.standard_normal((24, 4, 6, 8))).astype(np.float32)
@@ -107,12 +108,12 @@ def main():
         minmax_b=np.array(mm_b, np.float32),
         symmetric_pearson__reference=sym["pearson"], symmetric_spearman__reference=sym["spearman"],
         symmetric_kendall__reference=sym["kendall"],
-        symmetric_mi_binned__restatement=oracle.symmetric_field(3, fa, fb, num_bins=20, minmax_ref=mm_a, minmax_query=mm_b),
-        symmetric_mi_kraskov__restatement=oracle.symmetric_field(4, fa, fb, k=3),
+        symmetric_mi_binned__reference=ref.mi_symmetric_field(3, fa, fb, num_bins=20, minmax_ref=mm_a, minmax_query=mm_b),
+        symmetric_mi_kraskov__reference=ref.mi_symmetric_field(4, fa, fb, k=3),
         ensemble_mean__restatement=oracle.ensemble_stat(0, fb), ensemble_spread__restatement=oracle.ensemble_stat(1, fb),
         set_predicate_gt__restatement=oracle.set_predicate(0, 0.25, 8, 16, fa),
         set_predicate_le__restatement=oracle.set_predicate(3, -0.5, 12, 12, fa),
-        dkl_binned__restatement=oracle.dkl(0, fa, num_bins=16), dkl_knn__restatement=oracle.dkl(1, fa, k=2),
+        dkl_binned__reference=ref.dkl_field(0, fa, num_bins=16), dkl_knn__reference=ref.dkl_field(1, fa, k=2),
         tiled_member0__restatement=oracle.tile_field(fa[0]))
     print("two_fields_and_siblings: 192 voxels, cs=24")
     # known-answer vectors (computed by the reference object code)
@@ -127,11 +128,13 @@ def main():
 
 
 def record_reference_calls(ref, oracle):
-    """tests/golden/reference/calls.npz: the reference's answers to every call the oracle-vs-reference tests make
-    (test_oracle_vs_ref.py, test_pair_requests.py), keyed by the call's exact inputs -- those tests run against them
-    where oracle/_ref cannot be built."""
+    """tests/golden/reference/calls.npz and mi_calls.npz: the reference's answers to every call that the tests comparing
+    against it make (test_oracle_vs_ref.py, test_pair_requests.py; test_oracle_vs_ref_mi.py, test_gpu_reference_mi.py),
+    keyed by the call's exact inputs -- those tests run against them where oracle/_ref cannot be built."""
     import test_oracle_vs_ref as t
     import test_pair_requests as tp
+    import test_oracle_vs_ref_mi as tm
+    import test_gpu_reference_mi as tg
     rec = oracle_lib.RecordedReference(live=ref)
     for cs in t.FIELD_MEMBER_COUNTS:
         t.test_fields_bit_exact(oracle, rec, cs)
@@ -141,6 +144,24 @@ def record_reference_calls(ref, oracle):
         tp.test_oracle_pairs_vs_reference_primitives(oracle, rec, cs)
     rec.save(oracle_lib.RECORDED_CALLS)
     print(f"reference_calls: {len(rec.calls)} calls -> {oracle_lib.RECORDED_CALLS.stat().st_size} bytes")
+    tm.test_primitives_bit_exact(oracle, rec)
+    tm.test_kraskov_maximum(oracle, rec)
+    tm.test_binned_constant_data_is_zero_not_nan(oracle, rec)
+    tm.test_binned_infinite_samples_with_a_finite_range(oracle, rec)
+    tm.test_binned_value_exactly_one(oracle, rec)
+    tm.test_dkl_knn_duplicate_values_give_nan(oracle, rec)
+    tm.test_ksg2_marginal_count_of_one_evaluates_digamma_at_zero(oracle, rec)
+    for cs in (12, 64):
+        tm.test_binned_narrow_caller_range(oracle, rec, cs)
+    for cs in t.FIELD_MEMBER_COUNTS:
+        tm.test_fields_bit_exact(oracle, rec, cs)
+        tm.test_symmetric_fields_bit_exact(oracle, rec, cs)
+        tm.test_dkl_fields_bit_exact(oracle, rec, cs)
+    for cs in tp.PAIR_MEMBER_COUNTS:
+        tm.test_pair_requests_bit_exact(oracle, rec, cs)
+    tg.record_reference_calls(rec)
+    rec.save_mi(oracle_lib.RECORDED_MI_CALLS)
+    print(f"reference_mi_calls: {len(rec.mi_calls)} calls -> {oracle_lib.RECORDED_MI_CALLS.stat().st_size} bytes")
 
 
 if __name__ == "__main__":

@@ -7,8 +7,9 @@
  * oracle/corr_oracle.cpp bit-for-bit and (2) produce the golden vectors under tests/golden/
  * (oracle/make_golden.py), and may be used as the "reference"-kind CPU baseline of bench.py.
  *
- * Coverage: Pearson, Spearman, Kendall -- everything Correlation.cpp holds.  MutualInformation.cpp is
- * unbuildable here (needs boost, sgl, glm, which the image lacks) and is NOT part of this library.
+ * Coverage: Pearson, Spearman, Kendall -- everything Correlation.cpp holds.  MutualInformation.cpp and DKL.cpp are not
+ * part of this library: they need boost, sgl and glm and are compiled over stand-in headers into a library of their own
+ * (oracle/ref_mi_driver.cpp, oracle/standins/ -> oracle/_ref/libref_mi.so).
  *
  * The voxel loops below restate CorrelationCalculator.cpp:868-1025 (that file itself cannot be compiled: sgl::vk,
  * ImGui, VolumeData) and call the reference functions declared in Correlation.hpp.

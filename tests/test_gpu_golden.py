@@ -1,5 +1,6 @@
-"""GPU parity against the committed golden vectors (tests/golden, reference-object-code outputs for
-Pearson/Spearman/Kendall; restatement outputs for the MI estimators)."""
+"""GPU parity against the committed golden vectors (tests/golden): outputs of the reference's object code for
+Pearson/Spearman/Kendall (Correlation.cpp) and for the MI and DKL estimators (MutualInformation.cpp and DKL.cpp over
+oracle/standins/); restatement outputs for the sibling calculators."""
 from pathlib import Path
 
 import numpy as np
@@ -27,15 +28,15 @@ def test_gpu_matches_golden(engine, case):
     assert_bit_exact(run(Measure.SPEARMAN), d["spearman__reference"], f"{case}/spearman")
     assert_bit_exact(run(Measure.KENDALL), d["kendall__reference"], f"{case}/kendall")
     bk = dict(num_bins=80, minmax_ref=mm, minmax_query=mm)
-    assert_close(run(Measure.MUTUAL_INFORMATION_BINNED, **bk), d["mi_binned__restatement"], f"{case}/mi_binned")
-    assert_close(run(Measure.BINNED_MI_CORRELATION_COEFFICIENT, **bk), d["binned_mi_cc__restatement"],
+    assert_close(run(Measure.MUTUAL_INFORMATION_BINNED, **bk), d["mi_binned__reference"], f"{case}/mi_binned")
+    assert_close(run(Measure.BINNED_MI_CORRELATION_COEFFICIENT, **bk), d["binned_mi_cc__reference"],
                  f"{case}/binned_mi_cc")
-    assert_close(run(Measure.MUTUAL_INFORMATION_KRASKOV, k=k), d["mi_kraskov__restatement"], f"{case}/mi_kraskov")
-    assert_close(run(Measure.MUTUAL_INFORMATION_KRASKOV, k=min(3, max(cs - 1, 1))), d["mi_kraskov_k3__restatement"],
+    assert_close(run(Measure.MUTUAL_INFORMATION_KRASKOV, k=k), d["mi_kraskov__reference"], f"{case}/mi_kraskov")
+    assert_close(run(Measure.MUTUAL_INFORMATION_KRASKOV, k=min(3, max(cs - 1, 1))), d["mi_kraskov_k3__reference"],
                  f"{case}/mi_kraskov k=3")
     assert_close(run(Measure.MUTUAL_INFORMATION_KRASKOV, k=k, kraskov_estimator_index=2),
-                 d["mi_kraskov2__restatement"], f"{case}/mi_kraskov2")
-    assert_close(run(Measure.KMI_CORRELATION_COEFFICIENT, k=k), d["kmi_cc__restatement"], f"{case}/kmi_cc")
+                 d["mi_kraskov2__reference"], f"{case}/mi_kraskov2")
+    assert_close(run(Measure.KMI_CORRELATION_COEFFICIENT, k=k), d["kmi_cc__reference"], f"{case}/kmi_cc")
 
 
 def test_gpu_two_field_modes_and_siblings(engine):
@@ -50,13 +51,13 @@ def test_gpu_two_field_modes_and_siblings(engine):
     for name, m in (("pearson", Measure.PEARSON), ("spearman", Measure.SPEARMAN), ("kendall", Measure.KENDALL)):
         assert_bit_exact(engine.compute(m, symmetric=True), d[f"symmetric_{name}__reference"], f"symmetric {name}")
     assert_close(engine.compute(Measure.MUTUAL_INFORMATION_BINNED, symmetric=True, num_bins=20, minmax_ref=mm_a,
-                                minmax_query=mm_b), d["symmetric_mi_binned__restatement"], "symmetric binned")
+                                minmax_query=mm_b), d["symmetric_mi_binned__reference"], "symmetric binned")
     assert_close(engine.compute(Measure.MUTUAL_INFORMATION_KRASKOV, symmetric=True, k=3),
-                 d["symmetric_mi_kraskov__restatement"], "symmetric kraskov")
+                 d["symmetric_mi_kraskov__reference"], "symmetric kraskov")
     assert_bit_exact(engine.set_predicate(">", 0.25, 8, 16), d["set_predicate_gt__restatement"], "set predicate >")
     assert_bit_exact(engine.set_predicate("<=", -0.5, 12, 12), d["set_predicate_le__restatement"], "set predicate <=")
-    assert_close(engine.dkl("binned", num_bins=16), d["dkl_binned__restatement"], "dkl binned")
-    assert_close(engine.dkl("knn", k=2), d["dkl_knn__restatement"], "dkl knn")
+    assert_close(engine.dkl("binned", num_bins=16), d["dkl_binned__reference"], "dkl binned")
+    assert_close(engine.dkl("knn", k=2), d["dkl_knn__reference"], "dkl knn")
     lin = torch.from_numpy(fa[0].copy()).cuda()
     tiled = torch.empty(engine.tiled_element_count(), dtype=torch.float32, device="cuda")
     engine.tile_field_device(lin, tiled)

@@ -1,5 +1,6 @@
-"""CPU: the oracle against independent formulations (scipy / numpy / analytic).  This is the cross-check that stands
-in for a reference build of the two MI estimators (unbuildable here: boost, sgl, glm absent)."""
+"""CPU: the oracle against independent formulations (scipy / numpy / analytic).  The arithmetic of the MI and DKL
+estimators is pinned to the reference's object code in test_oracle_vs_ref_mi.py; that build replaces digamma, the k-NN
+search and the noise generator by stand-ins, and this is the cross-check of what those compute."""
 import math
 
 import numpy as np
