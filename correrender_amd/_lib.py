@@ -59,6 +59,7 @@ SYMBOLS = {
     "crf_bind_members_device_format": (C.c_int, [_VOIDP, C.c_int, C.POINTER(_VOIDP)]),
     "crf_member_format": (C.c_int, [_VOIDP]),
     "crf_last_member_format": (C.c_int, [_VOIDP]),
+    "crf_wide_copy_bytes": (C.c_size_t, [_VOIDP]),
     "crf_member_minmax": (C.c_int, [_VOIDP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "crf_member_minmax_divergent": (C.c_int, [_VOIDP, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "crf_upload_secondary_members": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),

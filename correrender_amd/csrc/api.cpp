@@ -134,9 +134,9 @@ int install_narrow_table(crf_context* c) {
     return CRF_OK;
 }
 
-// Members in a narrow native format: the fp32 copy that every kernel but the native Pearson field reads -- one owned
-// block plus the member table, converted on stream s at the first call that needs it (a Pearson-only user never pays
-// for it).  Dropped with the packed copy (drop_wide).
+// Members in a narrow native format: the fp32 copy that every kernel reads but the native Pearson field, the native
+// sibling reductions, the extrema and the reference gathers -- one owned block plus the member table, converted on
+// stream s at the first call that needs it (a user of those entry points alone never pays for it).  Dropped with the packed copy (drop_wide).
 int ensure_wide(crf_context* c, hipStream_t s) {
     if (c->format == CRF_MEMBER_F32 || !c->members.empty()) return CRF_OK;
     if (int r = bind_device(c)) return r;
@@ -166,6 +166,13 @@ int ensure_wide(crf_context* c, hipStream_t s) {
 bool native_pearson(const crf_context* c, const crf_params* p) {
     return c->format != CRF_MEMBER_F32 && p->measure == CRF_PEARSON && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 &&
            c->cs <= crf::kNarrowMaxMembers && c->narrow_aligned && !c->windowed;
+}
+
+// The sibling reductions (ensemble mean / spread, set predicate) read narrow members directly under the same condition
+// (kernels_stats.hip: ensemble_stat_narrow_kernel, set_predicate_narrow_kernel), at any member count.  The extrema and the
+// reference gathers read narrow members element by element and ask for nothing but a narrow format.
+bool native_reduction(const crf_context* c) {
+    return c->format != CRF_MEMBER_F32 && c->narrow_aligned && !c->windowed;
 }
 
 // Packs the members for the Pearson field if the layout policy asks for it (include/corrfield.h: crf_member_layout),
@@ -857,12 +864,14 @@ int ensure_host_ranges(crf_context* c, bool native) {
 }
 
 // The ensemble-stat, set-predicate and DKL device calls: launch(out, stream, timed launch) once, or once per window of
-// a >= 4 GiB grid (stopping at the first window that fails), as one timed launch.
+// a >= 4 GiB grid (stopping at the first window that fails), as one timed launch.  native: the launch reads the members in
+// their narrow format (native_reduction: never windowed), so no fp32 copy is built.
 template <class Launch>
-int run_windowed(crf_context* c, void* device_out, void* stream, Launch&& launch) {
+int run_windowed(crf_context* c, void* device_out, void* stream, bool native, Launch&& launch) {
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
-    if (int r = ensure_wide(c, s)) return r;
+    if (!native)
+        if (int r = ensure_wide(c, s)) return r;
     TimedLaunch timed(c);
     hipError_t e = hipSuccess;
     const int rc = for_each_window(c, static_cast<float*>(device_out), [&](float* o) {
@@ -1129,13 +1138,20 @@ int crf_member_format(const crf_context* c) { return c ? c->format : CRF_MEMBER_
 
 int crf_last_member_format(const crf_context* c) { return c ? c->last_format : CRF_MEMBER_F32; }
 
+size_t crf_wide_copy_bytes(const crf_context* c) {
+    if (!c || !c->wide_block) return 0;
+    return ((c->alloc_voxels + 63) & ~size_t(63)) * sizeof(float) * size_t(c->cs);  // ensure_wide's block
+}
+
 int crf_member_minmax(crf_context* c, float* out_min, float* out_max) {
     if (int r = check_ready(c)) return r;
     if (!out_min || !out_max) return fail(c, CRF_ERR_ARGUMENT, "null output");
     if (!c->minmax_valid) {
         if (int r = bind_device(c)) return r;
-        if (int r = ensure_wide(c, c->stream)) return r;
-        CRF_HIP(c, crf::launch_minmax(c->d_member_table, c->cs, c->num_voxels, c->d_minmax, c->stream));
+        if (c->format != CRF_MEMBER_F32)  // the narrow members as stored: no fp32 copy
+            CRF_HIP(c, crf::launch_minmax_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, c->d_minmax, c->stream));
+        else
+            CRF_HIP(c, crf::launch_minmax(c->d_member_table, c->cs, c->num_voxels, c->d_minmax, c->stream));
         uint32_t keys[2];
         CRF_HIP(c, hipMemcpyAsync(keys, c->d_minmax, sizeof keys, hipMemcpyDeviceToHost, c->stream));
         CRF_HIP(c, hipStreamSynchronize(c->stream));
@@ -1214,8 +1230,11 @@ int crf_gather_reference_device(crf_context* c, int x, int y, int z, void* devic
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
-    if (int r = ensure_wide(c, s)) return r;
-    CRF_HIP(c, crf::launch_gather_reference(c->d_member_table, c->cs, voxel, static_cast<float*>(device_out), s));
+    if (c->format != CRF_MEMBER_F32)  // the converted values of the narrow members: no fp32 copy
+        CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, voxel,
+                                                       static_cast<float*>(device_out), s));
+    else
+        CRF_HIP(c, crf::launch_gather_reference(c->d_member_table, c->cs, voxel, static_cast<float*>(device_out), s));
     return CRF_OK;
 }
 
@@ -1232,9 +1251,12 @@ int crf_gather_reference_rows_device(crf_context* c, const int32_t* xyz, int num
     }
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
-    if (int r = ensure_wide(c, s)) return r;
-    CRF_HIP(c, crf::launch_gather_reference_rows(c->d_member_table, c->cs, rows, num_rows,
-                                                 static_cast<float*>(device_rows), s));
+    if (c->format != CRF_MEMBER_F32)
+        CRF_HIP(c, crf::launch_gather_reference_rows_narrow(c->d_narrow_table, c->format, c->cs, rows, num_rows,
+                                                            static_cast<float*>(device_rows), s));
+    else
+        CRF_HIP(c, crf::launch_gather_reference_rows(c->d_member_table, c->cs, rows, num_rows,
+                                                     static_cast<float*>(device_rows), s));
     return CRF_OK;
 }
 
@@ -1256,9 +1278,10 @@ int gather_reference_to(crf_context* c, bool secondary, int x, int y, int z, flo
     size_t voxel;
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
-    if (!secondary)
-        if (int r = ensure_wide(c, s)) return r;
-    CRF_HIP(c, launch_gather_reference(secondary ? c->d_sec_table : c->d_member_table, c->cs, voxel, device_out, s));
+    if (!secondary && c->format != CRF_MEMBER_F32)
+        CRF_HIP(c, launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, voxel, device_out, s));
+    else
+        CRF_HIP(c, launch_gather_reference(secondary ? c->d_sec_table : c->d_member_table, c->cs, voxel, device_out, s));
     return CRF_OK;
 }
 
@@ -1575,7 +1598,11 @@ int crf_compute_ensemble_stat_device(crf_context* c, int stat, void* device_out,
     if (!device_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
     if (stat != CRF_ENSEMBLE_MEAN && stat != CRF_ENSEMBLE_SPREAD)
         return fail(c, CRF_ERR_ARGUMENT, fmt("unknown ensemble statistic %d", stat));
-    return run_windowed(c, device_out, stream, [&](float* o, hipStream_t s, TimedLaunch& t) {
+    const bool native = native_reduction(c);
+    return run_windowed(c, device_out, stream, native, [&](float* o, hipStream_t s, TimedLaunch& t) {
+        if (native)
+            return crf::launch_ensemble_stat_narrow(stat, c->d_narrow_table, c->format, c->cs, c->num_voxels, o, s, t.e0,
+                                                    t.e1, &t.info);
         return crf::launch_ensemble_stat(stat, c->d_member_table, c->cs, c->num_voxels, o, s, t.e0, t.e1, &t.info);
     });
 }
@@ -1590,7 +1617,11 @@ int crf_compute_set_predicate_device(crf_context* c, int op, float comparison_va
     if (!device_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
     if (op < CRF_CMP_GREATER || op > CRF_CMP_NOT_EQUAL)
         return fail(c, CRF_ERR_ARGUMENT, fmt("unknown comparison operator %d", op));
-    return run_windowed(c, device_out, stream, [&](float* o, hipStream_t s, TimedLaunch& t) {
+    const bool native = native_reduction(c);
+    return run_windowed(c, device_out, stream, native, [&](float* o, hipStream_t s, TimedLaunch& t) {
+        if (native)
+            return crf::launch_set_predicate_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, op, comparison_value,
+                                                    count_lower, count_upper, o, s, t.e0, t.e1, &t.info);
         return crf::launch_set_predicate(c->d_member_table, c->cs, c->num_voxels, op, comparison_value, count_lower,
                                          count_upper, o, s, t.e0, t.e1, &t.info);
     });
@@ -1619,7 +1650,7 @@ int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, v
     // psi(n) = -gamma + H_{n-1} (boost::math::digamma at positive integers, DKL.cpp:156)
     const double knn_const =
         estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 ? psi_int(c->cs) - psi_int(k) + std::log(2.0) : 0.0;
-    return run_windowed(c, device_out, stream, [&](float* o, hipStream_t s, TimedLaunch& t) {
+    return run_windowed(c, device_out, stream, false, [&](float* o, hipStream_t s, TimedLaunch& t) {
         return crf::launch_dkl(c->d_member_table, c->cs, c->num_voxels, estimator, num_bins, k, knn_const, c->scratch[0].workspace, o,
                                s, t.e0, t.e1, &t.info);
     });

@@ -37,7 +37,8 @@ struct crf_context {
     int max_vpt = 1;
     // primary members in a narrow native format (crf_upload_members_format / crf_bind_members_device_format): `narrow`
     // holds the cs device pointers and `members` stays empty until a call that needs fp32 members builds the widened
-    // copy (api.cpp: ensure_wide), one owned block; the Pearson field at 2..128 members reads `narrow` directly
+    // copy (api.cpp: ensure_wide), one owned block; the Pearson field at 2..128 members, the sibling reductions, the
+    // extrema and the reference gathers read `narrow` directly
     int format = CRF_MEMBER_F32;
     void* narrow_owned_block = nullptr;
     std::vector<const void*> narrow;

@@ -71,6 +71,40 @@ __device__ __forceinline__ float narrow_value(const void* base, size_t i) {
     }
 }
 
+// The same values out of a member's dword, for the kernels whose lanes own the VPL = 4 (8-bit) or 2 (16-bit)
+// consecutive voxels of one dword (kernels_pearson.hip: pearson_narrow_kernel, kernels_stats.hip): two voxels at a
+// time in packed fp32.  The integer formats' x / 255.0f, x / 65535.0f is exact_div (below) with a compile-time
+// reciprocal: x is an integer below 2^16 and the denominator a constant inside [2^-60, 2^60], its preconditions.
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+template <int FMT>
+constexpr int narrow_vpl() {
+    return FMT == CRF_MEMBER_U8 ? 4 : 2;
+}
+
+// voxels 2 h and 2 h + 1 of the lane out of a member's dword
+template <int FMT>
+__device__ __forceinline__ f2 narrow_pair(uint32_t w, int h) {
+    if constexpr (FMT == CRF_MEMBER_F16) {
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        const h2 v = __builtin_bit_cast(h2, w);
+        return f2{float(v[0]), float(v[1])};
+    } else {
+        constexpr float kDen = FMT == CRF_MEMBER_U8 ? 255.0f : 65535.0f;
+        constexpr float kRcp = 1.0f / kDen;
+        f2 x;
+        if constexpr (FMT == CRF_MEMBER_U8) {
+            x = f2{float((w >> (16 * h)) & 0xFFu), float((w >> (16 * h + 8)) & 0xFFu)};
+        } else {
+            x = f2{float(w & 0xFFFFu), float(w >> 16)};
+        }
+        const f2 rcp2 = {kRcp, kRcp}, den2 = {kDen, kDen};
+        const f2 q0 = x * rcp2;
+        const f2 rem = __builtin_elementwise_fma(-q0, den2, x);
+        return __builtin_elementwise_fma(rem, rcp2, q0);
+    }
+}
+
 __device__ __forceinline__ float load_ref(const RefSource& r, const float* const* __restrict__ members, int c) {
     if (r.values) return r.values[c];
     return (r.table ? r.table : members)[c][r.voxel];

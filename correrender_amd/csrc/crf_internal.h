@@ -179,6 +179,12 @@ hipError_t launch_widen_members(const void* const* d_narrow, int format, int cs,
 // d_out[c] = converted value of d_narrow[c][voxel]
 hipError_t launch_gather_reference_narrow(const void* const* d_narrow, int format, int cs, size_t voxel, float* d_out,
                                           hipStream_t s);
+// launch_gather_reference_rows / launch_minmax on narrow members (no alignment asked of the pointers beyond the
+// element's own): the rows hold converted values; the keys are those launch_minmax leaves for the converted values
+hipError_t launch_gather_reference_rows_narrow(const void* const* d_narrow, int format, int cs, const GatherRows& rows,
+                                               int num_rows, float* d_out, hipStream_t s);
+hipError_t launch_minmax_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, uint32_t* d_keys /*[2]*/,
+                                hipStream_t s);
 hipError_t launch_fill(float* d_out, size_t n, float value, hipStream_t s);
 hipError_t launch_abs(float* d_out, size_t n, hipStream_t s);  // in place |.| (CRF_FLAG_ABSOLUTE_VALUE on a field)
 
@@ -258,6 +264,15 @@ hipError_t launch_ensemble_stat(int kind, const float* const* d_members, int cs,
 hipError_t launch_set_predicate(const float* const* d_members, int cs, size_t num_voxels, int op, float comparison_value,
                                 int count_lower, int count_upper, float* d_out, hipStream_t s, hipEvent_t ev_begin,
                                 hipEvent_t ev_end, LaunchInfo* info);
+// The same on members in a narrow native format, read as stored (bit-identical to the fp32 launchers on the converted
+// values).  d_narrow as for launch_pearson_narrow: every pointer 4-byte aligned, num_voxels x element size below
+// kNarrowMaxBytes; any cs >= 1.  Main kernel and tail kernel are bracketed by one event pair.
+hipError_t launch_ensemble_stat_narrow(int kind, const void* const* d_narrow, int format, int cs, size_t num_voxels,
+                                       float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
+                                       LaunchInfo* info);
+hipError_t launch_set_predicate_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, int op,
+                                       float comparison_value, int count_lower, int count_upper, float* d_out,
+                                       hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 hipError_t launch_tile_field(const float* d_linear, float* d_tiled, int xs, int ys, int zs, hipStream_t s);
 
 // ---- kernels_dkl.hip: DKLCalculator (estimator 0 = binned, 1 = entropy k-NN) --------------------------------

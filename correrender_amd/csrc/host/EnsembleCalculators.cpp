@@ -61,13 +61,32 @@ crf_context* EnsembleReduceCalculator::residentContext(int timeStepIdx, int ense
     if (crf_set_grid(ctx, volumeData->getGridSizeX(), volumeData->getGridSizeY(), volumeData->getGridSizeZ(), cs))
         throwBackendError("crf_set_grid");
     std::vector<HostCacheEntry> entries;
-    std::vector<const float*> fields;
-    for (int c = 0; c < cs; c++) {
+    entries.reserve(size_t(cs));
+    for (int c = 0; c < cs; c++)
         entries.push_back(volumeData->getFieldEntryCpu(FieldType::SCALAR, fieldName, ensembleAxis ? timeStepIdx : c,
                                                        ensembleAxis ? c : ensembleIdx));
-        fields.push_back(entries.back()->data<float>());
+    // Members that all share one narrow native format go to the device as they are stored, like CorrelationCalculator's
+    // (crf_member_format: half or a quarter of the bytes cross the bus and stay resident, no float view is converted on
+    // the host, and the mean, spread and set predicate read them at that width); members of mixed formats take the
+    // float views.
+    const ScalarDataFormat native = entries[0]->getScalarDataFormatNative();
+    bool sameFormat = true;
+    for (const HostCacheEntry& entry : entries) sameFormat = sameFormat && entry->getScalarDataFormatNative() == native;
+    int format = CRF_MEMBER_F32;
+    if (sameFormat && native != ScalarDataFormat::FLOAT)
+        format = native == ScalarDataFormat::BYTE ? CRF_MEMBER_U8 : native == ScalarDataFormat::SHORT ? CRF_MEMBER_U16 : CRF_MEMBER_F16;
+    if (format != CRF_MEMBER_F32) {
+        std::vector<const void*> natives;
+        natives.reserve(size_t(cs));
+        for (const HostCacheEntry& entry : entries) natives.push_back(entry->getDataNative());
+        if (crf_upload_members_format(ctx, format, natives.data())) throwBackendError("crf_upload_members_format");
+    } else {
+        std::vector<const float*> fields;
+        fields.reserve(size_t(cs));
+        for (const HostCacheEntry& entry : entries) fields.push_back(entry->data<float>());
+        if (crf_upload_members(ctx, fields.data())) throwBackendError("crf_upload_members");
     }
-    if (crf_upload_members(ctx, fields.data())) throwBackendError("crf_upload_members");
+    residentFormat = format;
     residentGeneration = volumeData->getDataGeneration();
     residentField = fieldName;
     residentCs = cs;

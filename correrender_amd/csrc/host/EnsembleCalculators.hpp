@@ -33,6 +33,9 @@ public:
     FilterDevice getFilterDevice() override { return FilterDevice::CPU; }
     void setSettings(const SettingsMap& settings) override;
     void getSettings(SettingsMap& settings) override;
+    /// crf_member_format of the members the last calculateCpu left resident on the device: a narrow format when every
+    /// member entry shared it, else CRF_MEMBER_F32.
+    int getResidentMemberFormat() const { return residentFormat; }
 
 protected:
     /// Member axis: the ensemble members (EnsembleMean/Spread/DKL always, :98 / DKLCalculator.cpp:138); SetPredicate may
@@ -52,6 +55,7 @@ protected:
     std::string residentField;
     int residentFixedIdx = -1, residentCs = -1;
     bool residentEnsembleAxis = true;
+    int residentFormat = CRF_MEMBER_F32;
 };
 
 class EnsembleMeanCalculator : public EnsembleReduceCalculator {

@@ -4,6 +4,7 @@
 //                                   VolumeData.cpp:1632-1670, CorrelationCalculator.cpp:822-829)
 //   * synthetic box-ensemble fill  (recipe of scripts/generate_synth_box_ensembles.py:57-136; input generation only)
 #include <algorithm>
+#include <type_traits>
 
 #include "crf_device.h"
 #include "crf_internal.h"
@@ -103,6 +104,37 @@ hipError_t launch_gather_reference_rows(const float* const* d_members, int cs, c
     return hipGetLastError();
 }
 
+template <int FMT>
+__global__ void gather_reference_rows_narrow_kernel(const void* const* __restrict__ members, int cs, GatherRows rows,
+                                                    float* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blockIdx.y;
+    if (c < cs) {
+        const size_t voxel = rows.voxel[r];
+        out[size_t(r) * size_t(cs) + c] = voxel == kNoVoxel ? 0.0f : narrow_value<FMT>(members[c], voxel);
+    }
+}
+
+hipError_t launch_gather_reference_rows_narrow(const void* const* d_narrow, int format, int cs, const GatherRows& rows,
+                                               int num_rows, float* d_out, hipStream_t s) {
+    if (num_rows <= 0) return hipSuccess;
+    if (num_rows > kMaxGatherRows) return hipErrorInvalidValue;
+    const dim3 grid((cs + 63) / 64, num_rows), block(64);
+    switch (format) {
+        case CRF_MEMBER_U8:
+            hipLaunchKernelGGL(gather_reference_rows_narrow_kernel<CRF_MEMBER_U8>, grid, block, 0, s, d_narrow, cs, rows, d_out);
+            break;
+        case CRF_MEMBER_U16:
+            hipLaunchKernelGGL(gather_reference_rows_narrow_kernel<CRF_MEMBER_U16>, grid, block, 0, s, d_narrow, cs, rows, d_out);
+            break;
+        case CRF_MEMBER_F16:
+            hipLaunchKernelGGL(gather_reference_rows_narrow_kernel<CRF_MEMBER_F16>, grid, block, 0, s, d_narrow, cs, rows, d_out);
+            break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Order-preserving float -> uint32 key so that unsigned atomicMin/atomicMax order like the floats do.
 __device__ __forceinline__ uint32_t float_to_key(float f) {
@@ -168,6 +200,87 @@ hipError_t launch_minmax(const float* const* d_members, int cs, size_t num_voxel
     if (blocks > 64) blocks = 64;  // 64 blocks x cs members >> 256 CUs
     hipLaunchKernelGGL(minmax_kernel, dim3(unsigned(blocks), unsigned(cs)), dim3(256), 0, s, d_members, num_voxels,
                        d_keys);
+    return hipGetLastError();
+}
+
+// The extrema of members in a narrow native format, read as stored: the keys launch_minmax leaves for the converted
+// values.  u8 / u16 reduce the integer codes and convert the two winners (the conversion is strictly increasing);
+// float16 converts first, skips NaNs and reduces the fp32 kernel's keys, in which -0 orders below +0 exactly as in its
+// fminf / fmaxf.  Same grid and atomics scheme as minmax_kernel.  Nothing is asked of the pointers beyond the element's
+// own alignment: the elements before the first 16-byte boundary and behind the last whole 16 bytes are read one by one.
+template <int FMT>
+__global__ __launch_bounds__(256) void minmax_narrow_kernel(const void* const* __restrict__ members, size_t num_voxels,
+                                                            uint32_t* __restrict__ keys) {
+    typedef typename std::conditional<FMT == CRF_MEMBER_U8, uint8_t, uint16_t>::type elem_t;
+    constexpr size_t kPerVector = 16 / sizeof(elem_t);
+    const elem_t* __restrict__ p = static_cast<const elem_t*>(members[blockIdx.y]);
+    uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+    const auto see = [&mn, &mx](uint32_t code) {
+        uint32_t k = code;
+        if constexpr (FMT == CRF_MEMBER_F16) {
+            const float f = float(__builtin_bit_cast(_Float16, uint16_t(code)));
+            if (f != f) return;
+            k = float_to_key(f);
+        }
+        mn = k < mn ? k : mn;
+        mx = k > mx ? k : mx;
+    };
+    const uintptr_t address = reinterpret_cast<uintptr_t>(p);
+    size_t head = ((16u - (address & 15u)) & 15u) / sizeof(elem_t);
+    if (address % sizeof(elem_t) != 0 || head > num_voxels) head = num_voxels;  // (no 16-byte boundary to reach)
+    const size_t vectors = (num_voxels - head) / kPerVector;
+    const size_t stride = size_t(gridDim.x) * blockDim.x;
+    const size_t t = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    for (size_t i = t; i < head; i += stride) see(p[i]);
+    const uint4* __restrict__ p4 = reinterpret_cast<const uint4*>(p + head);
+    for (size_t i = t; i < vectors; i += stride) {
+        const uint4 v = p4[i];
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if constexpr (FMT == CRF_MEMBER_U8) {
+                see(d[j] & 0xFFu);
+                see((d[j] >> 8) & 0xFFu);
+                see((d[j] >> 16) & 0xFFu);
+                see(d[j] >> 24);
+            } else {
+                see(d[j] & 0xFFFFu);
+                see(d[j] >> 16);
+            }
+        }
+    }
+    for (size_t i = head + vectors * kPerVector + t; i < num_voxels; i += stride) see(p[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t omn = __shfl_xor(mn, off, 64), omx = __shfl_xor(mx, off, 64);
+        mn = omn < mn ? omn : mn;
+        mx = omx > mx ? omx : mx;
+    }
+    if ((threadIdx.x & 63) == 0 && mn <= mx) {  // false only when every value seen was NaN / nothing was seen
+        if constexpr (FMT != CRF_MEMBER_F16) {
+            const elem_t lo = elem_t(mn), hi = elem_t(mx);
+            mn = float_to_key(narrow_value<FMT>(&lo, 0));
+            mx = float_to_key(narrow_value<FMT>(&hi, 0));
+        }
+        atomicMin(&keys[0], mn);
+        atomicMax(&keys[1], mx);
+    }
+}
+
+hipError_t launch_minmax_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, uint32_t* d_keys,
+                                hipStream_t s) {
+    if (cs <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(1), 0, s, d_keys);
+    size_t blocks = (num_voxels * member_format_bytes(format) / 16 + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 64) blocks = 64;
+    const dim3 grid{unsigned(blocks), unsigned(cs)}, block(256);
+    switch (format) {
+        case CRF_MEMBER_U8: hipLaunchKernelGGL(minmax_narrow_kernel<CRF_MEMBER_U8>, grid, block, 0, s, d_narrow, num_voxels, d_keys); break;
+        case CRF_MEMBER_U16: hipLaunchKernelGGL(minmax_narrow_kernel<CRF_MEMBER_U16>, grid, block, 0, s, d_narrow, num_voxels, d_keys); break;
+        case CRF_MEMBER_F16: hipLaunchKernelGGL(minmax_narrow_kernel<CRF_MEMBER_F16>, grid, block, 0, s, d_narrow, num_voxels, d_keys); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -97,7 +97,6 @@ __device__ __forceinline__ void store_vec(float* p, const float (&src)[VPT]) {
 // launch_pearson pads cs to the next multiple of this: only the last granule of a guarded instantiation can be padding
 constexpr int pad_granule(int cs_pad) { return cs_pad <= 16 ? 8 : cs_pad <= 128 ? 16 : 32; }
 
-typedef float f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
 
 template <int CS_PAD, bool EXACT>
@@ -733,34 +732,7 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_split_kernel(const flo
 // Guarded slots (the last granule of a guarded instantiation) are stepped over in uniform branches, loads included: a
 // skipped slot is the +0 that pearson_reg_kernel adds for it in every pass.
 // ---------------------------------------------------------------------------------------------------------
-template <int FMT>
-constexpr int narrow_vpl() {
-    return FMT == CRF_MEMBER_U8 ? 4 : 2;
-}
-
-// voxels 2 h and 2 h + 1 of the lane out of a member's dword
-template <int FMT>
-__device__ __forceinline__ f2 narrow_pair(uint32_t w, int h) {
-    if constexpr (FMT == CRF_MEMBER_F16) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        const h2 v = __builtin_bit_cast(h2, w);
-        return f2{float(v[0]), float(v[1])};
-    } else {
-        constexpr float kDen = FMT == CRF_MEMBER_U8 ? 255.0f : 65535.0f;
-        constexpr float kRcp = 1.0f / kDen;
-        f2 x;
-        if constexpr (FMT == CRF_MEMBER_U8) {
-            x = f2{float((w >> (16 * h)) & 0xFFu), float((w >> (16 * h + 8)) & 0xFFu)};
-        } else {
-            x = f2{float(w & 0xFFFFu), float(w >> 16)};
-        }
-        const f2 rcp2 = {kRcp, kRcp}, den2 = {kDen, kDen};
-        const f2 q0 = x * rcp2;
-        const f2 rem = __builtin_elementwise_fma(-q0, den2, x);
-        return __builtin_elementwise_fma(rem, rcp2, q0);
-    }
-}
-
+// (narrow_vpl and narrow_pair: crf_device.h, shared with the sibling reductions of kernels_stats.hip)
 template <int FMT, int CS_PAD, bool EXACT, int MIN_WAVES>
 __global__ __launch_bounds__(256, MIN_WAVES) void pearson_narrow_kernel(const void* const* __restrict__ members,
                                                                         const float* __restrict__ prep,

@@ -120,9 +120,10 @@ class CorrField:
         """members: cs torch CUDA tensors (or one [cs, ...] tensor), each holding one volume; borrowed.  The dtype decides
         the member format: float32, or float16 / uint16 / uint8 read natively (see upload_members); any other raises.
         The native Pearson kernel loads whole dwords, so every narrow member must start on a 4-byte boundary: the rows of
-        a plain [cs, n] uint8 or 16-bit tensor do only when n * itemsize is a multiple of 4.  Otherwise every evaluation,
-        the Pearson field included, runs on the fp32 copy (cs * n floats of device memory; last_member_format() says
-        "f32") -- pad the row stride, or use upload_members, whose copy is aligned."""
+        a plain [cs, n] uint8 or 16-bit tensor do only when n * itemsize is a multiple of 4.  Otherwise every per-voxel
+        evaluation, the Pearson field, ensemble_stat and set_predicate included, runs on the fp32 copy (cs * n floats of
+        device memory; last_member_format() says "f32", wide_copy_bytes() its size) -- pad the row stride, or use
+        upload_members, whose copy is aligned.  member_minmax and the reference gathers need no alignment."""
         tensors = [members[i] for i in range(self.cs)]
         formats = {_member_format(t.dtype) for t in tensors}
         if len(formats) != 1:
@@ -146,6 +147,12 @@ class CorrField:
         """The format the per-voxel kernel of the last field evaluation read: the members' own when the Pearson field
         read narrow members natively, "f32" when it ran on fp32 members or on the fp32 copy of narrow ones."""
         return MEMBER_FORMATS[self._lib.crf_last_member_format(self._ctx)]
+
+    def wide_copy_bytes(self) -> int:
+        """Bytes of the fp32 copy of narrow members that the context holds right now (0: none).  The Pearson field at
+        2..128 members, ensemble_stat, set_predicate, member_minmax and the reference gathers read narrow members as
+        stored and never build it; every other evaluation does, at its first call."""
+        return int(self._lib.crf_wide_copy_bytes(self._ctx))
 
     def member_minmax(self):
         mn, mx = C.c_float(), C.c_float()

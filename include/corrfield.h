@@ -128,7 +128,7 @@ const char* crf_last_error(const crf_context* ctx);
 /* ABI version of this header, bumped on incompatible change. */
 int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_minmax_divergent; added since, compatibly:
                                   crf_upload_members_format, crf_bind_members_device_format, crf_member_format,
-                                  crf_last_member_format;
+                                  crf_last_member_format, crf_wide_copy_bytes;
                                4: crf_group_* (several devices behind one caller thread), crf_set_kraskov_noise;
                                3: crf_params.reserved[0] became prepared_slot (same layout; 0 keeps the old meaning) */
 
@@ -149,10 +149,19 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *   - The Pearson field (CRF_PEARSON without CRF_FLAG_SYMMETRIC) at 2..128 members reads the narrow members directly
  *     (pearson_narrow_kernel); crf_last_member_format then returns the narrow format and crf_last_member_layout RAW
  *     (crf_set_member_layout has no effect on narrow members: the packed copy is an fp32 format).
- *   - Everything else runs on an fp32 copy of the members that the context builds on the compute stream at the first
+ *   - The sibling reductions (crf_compute_ensemble_stat[_device], crf_compute_set_predicate[_device]) read the narrow
+ *     members directly at any member count (ensemble_stat_narrow_kernel, set_predicate_narrow_kernel, reported by
+ *     crf_last_kernel_name; crf_last_member_format speaks of field evaluations only and is left alone).  Like the
+ *     Pearson field they load whole dwords, so borrowed members that are not all 4-byte aligned take the fp32 copy.
+ *   - crf_member_minmax and the reference gathers (crf_gather_reference, crf_gather_reference_device,
+ *     crf_gather_reference_rows_device) read the narrow members directly, whatever their alignment.
+ *   - Everything else -- the rank, mutual-information, DKL, symmetric and pair-request evaluations, and the Pearson field
+ *     above 128 members -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
  *     call that needs it (one owned block of cs x xs*ys*zs floats; CRF_ERR_DEVICE naming the copy and its size if it
  *     cannot be allocated) and drops in crf_set_grid, upload, bind and crf_members_changed; crf_last_member_format then
- *     returns CRF_MEMBER_F32.  So does the Pearson field over borrowed members that are not all 4-byte aligned.
+ *     returns CRF_MEMBER_F32.  So do the Pearson field and the sibling reductions over borrowed members that are not all
+ *     4-byte aligned.  A context that only runs the entry points of the three items above never builds the copy;
+ *     crf_wide_copy_bytes tells.
  *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.  Secondary members are fp32 only.
  *     crf_group_* evaluations on a context that holds narrow members: CRF_ERR_UNSUPPORTED.
  * format == CRF_MEMBER_F32 behaves exactly like crf_upload_members / crf_bind_members_device, which set the format to
@@ -167,6 +176,7 @@ int crf_upload_members_format(crf_context* ctx, int format, const void* const* h
 int crf_bind_members_device_format(crf_context* ctx, int format, const void* const* device_members);
 int crf_member_format(const crf_context* ctx);      /* format of the bound primary members */
 int crf_last_member_format(const crf_context* ctx); /* format the per-voxel kernel of the last field evaluation read */
+size_t crf_wide_copy_bytes(const crf_context* ctx);  /* bytes of the fp32 copy of narrow members held right now; 0 if none or ctx == NULL */
 /* min of per-member minima / max of per-member maxima over the local grid (CorrelationCalculator.cpp:822-829 on
  * top of VolumeData::getMinMaxScalarFieldValue, VolumeData.cpp:1632-1670); computed on the device, cached until
  * the members change. */
