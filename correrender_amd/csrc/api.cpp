@@ -519,8 +519,7 @@ int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream
     }
     if (e == hipErrorNotSupported) {
         if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, c->num_voxels))) return r;
-        const crf::PairArgs a{p->measure, p->num_bins, p->k, 0, 1, p->min_ref, p->max_ref, p->min_query, p->max_query,
-                              kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
+        const crf::PairArgs a{p->measure, p->num_bins, p->k, 0, kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
         e = crf::launch_pair_requests(c->d_member_table, c->d_sec_table, c->cs, c->xs, c->ys, c->num_voxels, nullptr,
                                       c->num_voxels, a, c->d_tables, c->scratch[0].workspace, out, s);
         kernel = "pair_request_kernel";
@@ -1532,7 +1531,7 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_QUERY_FROM_SECONDARY needs secondary members (crf_upload_secondary_members)");
         members_j = c->d_sec_table;
     }
-    const crf::PairArgs a{p->measure, p->num_bins, p->k, (p->flags & CRF_FLAG_ABSOLUTE_VALUE) ? 1 : 0, 0, 0.f, 0.f, 0.f, 0.f,
+    const crf::PairArgs a{p->measure, p->num_bins, p->k, (p->flags & CRF_FLAG_ABSOLUTE_VALUE) ? 1 : 0,
                           kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
     // Spearman / Kendall up to 128 members: the sort-based two-vector kernels (kernels_symmetric.hip) in request mode
     hipError_t e = hipErrorNotSupported;

@@ -284,9 +284,7 @@ hipError_t launch_dkl(const float* const* d_members, int cs, size_t num_voxels, 
 // pair-request mode (kernels_generic.hip): requests = 8 uint32 each {xi,yi,zi,i,xj,yj,zj,j}; voxel i is read from
 // d_members_i, voxel j from d_members_j.  d_requests == nullptr: request r = voxel pair (r, r) (symmetric field mode).
 struct PairArgs {
-    int measure, num_bins, k, use_abs;
-    int fixed_ranges;  // binned MI: 0 = normalise with the pair's own extrema (HEBChart), 1 = with the ranges below
-    float min_ref, max_ref, min_query, max_query;
+    int measure, num_bins, k, use_abs;  // binned MI normalises with the pair's own extrema (HEBChart)
     double kraskov_c;  // psi(k) (pair requests are KSG-1), host-evaluated like KraskovArgs::c_term
 };
 size_t pair_workspace_bytes(int cs, size_t num_requests);
