@@ -122,8 +122,12 @@ const char* format_name(int format) {
 }
 
 int install_narrow_table(crf_context* c) {
-    c->narrow_aligned = true;
-    for (const void* p : c->narrow) c->narrow_aligned = c->narrow_aligned && (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
+    c->narrow_aligned = c->narrow_element_aligned = true;
+    const uintptr_t element_mask = crf::member_format_bytes(c->format) - 1;
+    for (const void* p : c->narrow) {
+        c->narrow_aligned = c->narrow_aligned && (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
+        c->narrow_element_aligned = c->narrow_element_aligned && (reinterpret_cast<uintptr_t>(p) & element_mask) == 0;
+    }
     CRF_HIP(c, hipMemcpyAsync(c->d_narrow_table, c->narrow.data(), sizeof(void*) * size_t(c->cs), hipMemcpyHostToDevice,
                               c->stream));
     CRF_HIP(c, hipStreamSynchronize(c->stream));
@@ -134,8 +138,8 @@ int install_narrow_table(crf_context* c) {
     return CRF_OK;
 }
 
-// Members in a narrow native format: the fp32 copy that every kernel reads but the native Pearson field, the native
-// sibling reductions, the extrema and the reference gathers -- one owned block plus the member table, converted on
+// Members in a narrow native format: the fp32 copy that every kernel reads but the native Pearson and Kendall fields, the
+// native sibling reductions, the extrema and the reference gathers -- one owned block plus the member table, converted on
 // stream s at the first call that needs it (a user of those entry points alone never pays for it).  Dropped with the packed copy (drop_wide).
 int ensure_wide(crf_context* c, hipStream_t s) {
     if (c->format == CRF_MEMBER_F32 || !c->members.empty()) return CRF_OK;
@@ -167,6 +171,16 @@ bool native_pearson(const crf_context* c, const crf_params* p) {
     return c->format != CRF_MEMBER_F32 && p->measure == CRF_PEARSON && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 &&
            c->cs <= crf::kNarrowMaxMembers && c->narrow_aligned && !c->windowed;
 }
+
+// The Kendall field reads them with one byte / short load per element (kernels_rank_narrow.hip: kendall_narrow_kernel),
+// so it asks for the element's own alignment only.
+bool native_kendall(const crf_context* c, const crf_params* p) {
+    return c->format != CRF_MEMBER_F32 && p->measure == CRF_KENDALL && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 &&
+           c->cs <= crf::kNarrowMaxMembers && c->narrow_element_aligned && !c->windowed;
+}
+
+// the per-voxel kernel of this field evaluation reads the narrow members (c->d_narrow_table), no fp32 copy
+bool native_field(const crf_context* c, const crf_params* p) { return native_pearson(c, p) || native_kendall(c, p); }
 
 // The sibling reductions (ensemble mean / spread, set predicate) read narrow members directly under the same condition
 // (kernels_stats.hip: ensemble_stat_narrow_kernel, set_predicate_narrow_kernel), at any member count.  The extrema and the
@@ -639,7 +653,7 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
     float* out = static_cast<float*>(device_out);
-    const bool native = native_pearson(c, p);
+    const bool native = native_field(c, p);
     if (ov && c->format != CRF_MEMBER_F32)
         return fail(c, CRF_ERR_UNSUPPORTED, "a direct reference read needs fp32 members");
     if (!native)
@@ -743,6 +757,15 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
         }
         case CRF_SPEARMAN:
         case CRF_KENDALL:
+            if (native) {  // Kendall on narrow members: one pass, no todo list; the reference side is fp32 as ever
+                if ((phase & 1u) && !ref.values) {
+                    CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, ref.voxel, c->d_ref, s));
+                    ref.values = c->d_ref;
+                }
+                e = crf::launch_kendall_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, ref, prep, out, s, e0, e1,
+                                               info);
+                break;
+            }
             if (c->cs > 16)
                 if (int r = ensure_todo(c)) return r;
             e = (p->measure == CRF_SPEARMAN ? crf::launch_spearman : crf::launch_kendall)(
@@ -798,8 +821,9 @@ int apply_abs(crf_context* c, const crf_params* p, void* device_out, void* strea
 // first voxel), so that every per-voxel kernel can be launched on a range without knowing about ranges.  Range lengths
 // are multiples of 1024 voxels (4 KiB: every range stays as aligned as the members themselves) and shrink towards the
 // end: the copy of the last range into the caller's buffer is the only host work no kernel hides.
-// native: the tables hold the narrow members' pointers (the native Pearson field), advanced by whole elements; a range
-// starts at a multiple of 1024 voxels, so they stay 4-byte aligned and every range but the last is whole dwords.
+// native: the tables hold the narrow members' pointers (the native Pearson and Kendall fields), advanced by whole
+// elements; a range starts at a multiple of 1024 voxels, so they stay as aligned as the members (4 bytes for Pearson, the
+// element for Kendall) and every range but the last is whole dwords.
 int ensure_host_ranges(crf_context* c, bool native) {
     if (c->host_chunks > 0 && c->chunk_native == native) return CRF_OK;
     c->host_chunks = 0;
@@ -1331,7 +1355,7 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
         if (int r = compute_device_ex(c, p, device_reference_values, c->d_out, nullptr, ov)) return r;
         return copy_result_to_host(c, c->d_out, host_out, c->alloc_voxels);
     }
-    const bool native = native_pearson(c, p);
+    const bool native = native_field(c, p);
     if (!native)
         if (int r = ensure_wide(c, c->stream)) return r;  // (the second stream is ordered behind the preparation below)
     if (int r = ensure_host_ranges(c, native)) return r;

@@ -310,7 +310,76 @@ struct SortNet32<128> {
 #include "sortnet.inc"
     }
 };
+template <>
+struct SortNet32<8> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[8]) {
+#define CRF_SORTNET_N 8
+#include "sortnet.inc"
+    }
+};
+template <>
+struct SortNet32<24> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[24]) {
+#define CRF_SORTNET_N 24
+#include "sortnet.inc"
+    }
+};
+template <>
+struct SortNet32<40> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[40]) {
+#define CRF_SORTNET_N 40
+#include "sortnet.inc"
+    }
+};
+template <>
+struct SortNet32<56> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[56]) {
+#define CRF_SORTNET_N 56
+#include "sortnet.inc"
+    }
+};
+template <>
+struct SortNet32<72> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[72]) {
+#define CRF_SORTNET_N 72
+#include "sortnet.inc"
+    }
+};
+template <>
+struct SortNet32<88> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[88]) {
+#define CRF_SORTNET_N 88
+#include "sortnet.inc"
+    }
+};
+template <>
+struct SortNet32<104> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[104]) {
+#define CRF_SORTNET_N 104
+#include "sortnet.inc"
+    }
+};
+template <>
+struct SortNet32<120> {
+    static __device__ __forceinline__ void sort(uint32_t (&a)[120]) {
+#define CRF_SORTNET_N 120
+#include "sortnet.inc"
+    }
+};
 #undef CRF_CE
+
+// Ends a sorting network for the compiler: an empty asm "modifies" every element, so nothing that follows is mixed into the
+// network's last stages.  Left alone the compiler starts the scans / searches that consume the sorted array while the last
+// exchanges are still pending, the live ranges of both overlap, and a network over N values needs ~2N registers
+// (spearman_u32_kernel: 116 B of scratch per lane at 128 members, 25.1 -> 21.5 ms at 512^3 x 128 once they were gone;
+// mi_binned_kernel: 40 B of scratch at 64 / 128 members gone, three waves per SIMD instead of two at 96 members: 2.33 ->
+// 2.15 ms at 256^3).  Measured neutral for the other rank kernels, slightly negative (+2 %) for the two-field kernels of
+// kernels_symmetric*.hip, which therefore do without it.
+template <class T, int N>
+__device__ __forceinline__ void pin_array(T (&a)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; i++) asm volatile("" : "+v"(a[i]));
+}
 
 // Correctly rounded fp32 quotients a/b for MANY numerators and ONE denominator (the voxel's standard deviation) without
 // the ~10-instruction IEEE division expansion per element: with rcp = RN(1/b) (one true division),

@@ -157,9 +157,10 @@ hipError_t launch_pack_members(const float* const* d_members, int cs, size_t num
                                unsigned char* body, uint32_t* d_fallbacks, hipStream_t s);
 // ---- narrow primary members (include/corrfield.h: crf_member_format) ---------------------------------------------
 // The value the calculators see of a u8 / u16 / f16 element is float(b) / 255.0f, float(s) / 65535.0f, float(h)
-// (reference: src/Volume/Cache/HostCacheEntry.cpp:107-176).  The Pearson field at 2..kNarrowMaxMembers members reads
-// such members directly (kernels_pearson.hip: pearson_narrow_kernel); everything else runs on an fp32 copy that
-// launch_widen_members builds (kernels_common.hip).
+// (reference: src/Volume/Cache/HostCacheEntry.cpp:107-176).  The Pearson and the Kendall field at 2..kNarrowMaxMembers
+// members read such members directly (kernels_pearson.hip: pearson_narrow_kernel; kernels_rank_narrow.hip:
+// kendall_narrow_kernel), and so do the sibling reductions, the extrema and the gathers; everything else runs on an fp32
+// copy that launch_widen_members builds (kernels_common.hip).
 constexpr int kNarrowMaxMembers = 128;
 // A narrow member must be smaller than this: the native kernel's 32-bit voxel index and byte offset of the last block's
 // surplus lanes (up to 1020 voxels past the end) must not wrap.
@@ -197,6 +198,17 @@ hipError_t launch_spearman(const float* const* d_members, int cs, size_t num_vox
 hipError_t launch_kendall(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                           float* d_prep, uint32_t* d_todo, float* d_out, hipStream_t s, hipEvent_t ev_begin,
                           hipEvent_t ev_end, LaunchInfo* info);
+// stride of kendall_prep_kernel's tables at 2..128 members: the same for a preparation and any later evaluation from it
+constexpr int pad_pow2(int cs) { return cs <= 8 ? 8 : cs <= 16 ? 16 : cs <= 32 ? 32 : cs <= 64 ? 64 : 128; }
+
+// ---- kernels_rank_narrow.hip: Kendall on narrow members, read as stored ------------------------------------------------
+// One kernel, one pass, ties included (no todo list): 2 <= cs <= kNarrowMaxMembers, bit-identical to launch_kendall on the
+// converted values.  d_narrow: cs device pointers to num_voxels elements of `format`, each aligned to its element (no
+// more); num_voxels x element size below kNarrowMaxBytes.  ref.values holds the cs reference values (fp32, any values)
+// when ref.prepare(); d_prep gets launch_kendall_prep's tables with stride pad_pow2(cs).
+hipError_t launch_kendall_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, const RefSource& ref,
+                                 float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
+                                 LaunchInfo* info);
 
 // ---- kernels_binned.hip / kernels_kraskov.hip -------------------------------------------------------------------
 struct BinnedArgs {

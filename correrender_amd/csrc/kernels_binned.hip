@@ -30,19 +30,6 @@
 
 namespace crf {
 
-// Ends a sorting network for the compiler: an empty asm "modifies" every element, so nothing that follows is mixed into the
-// network's last stages.  Left alone the compiler starts the scans / searches that consume the sorted array while the last
-// exchanges are still pending, the live ranges of both overlap, and a network over N values needs ~2N registers
-// (spearman_u32_kernel: 116 B of scratch per lane at 128 members, 25.1 -> 21.5 ms at 512^3 x 128 once they were gone;
-// mi_binned_kernel: 40 B of scratch at 64 / 128 members gone, three waves per SIMD instead of two at 96 members: 2.33 ->
-// 2.15 ms at 256^3).  Measured neutral for the other rank kernels, slightly negative (+2 %) for the two-field kernels of
-// kernels_symmetric*.hip, which therefore do without it.
-template <class T, int N>
-__device__ __forceinline__ void pin_array(T (&a)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; i++) asm volatile("" : "+v"(a[i]));
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Binned MI: reference-side preparation.
 //   prep (int32 view): [0, N) b0_e (kInvalidBin when the normalised reference value is NaN), [N] = 1 if every reference

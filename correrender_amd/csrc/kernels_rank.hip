@@ -29,19 +29,6 @@
 
 namespace crf {
 
-// Ends a sorting network for the compiler: an empty asm "modifies" every element, so nothing that follows is mixed into the
-// network's last stages.  Left alone the compiler starts the scans / searches that consume the sorted array while the last
-// exchanges are still pending, the live ranges of both overlap, and a network over N values needs ~2N registers
-// (spearman_u32_kernel: 116 B of scratch per lane at 128 members, 25.1 -> 21.5 ms at 512^3 x 128 once they were gone;
-// mi_binned_kernel: 40 B of scratch at 64 / 128 members gone, three waves per SIMD instead of two at 96 members: 2.33 ->
-// 2.15 ms at 256^3).  Measured neutral for the other rank kernels, slightly negative (+2 %) for the two-field kernels of
-// kernels_symmetric*.hip, which therefore do without it.
-template <class T, int N>
-__device__ __forceinline__ void pin_array(T (&a)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; i++) asm volatile("" : "+v"(a[i]));
-}
-
 constexpr uint32_t kPadKey = 0xFFFFFFFFu;  // sorts after every real value (orderable_key(+inf) = 0xFF800000)
 
 // NaNs sort to the ends: a positive NaN has an orderable key above key(+inf) = 0xFF800000, a negative NaN one below
@@ -584,51 +571,6 @@ __global__ __launch_bounds__(64, MIN_WAVES) void spearman_split_kernel(const flo
         }
     }
 }
-
-// u32 networks for the member counts between the ones crf_device.h instantiates (sortnet.inc has every multiple of 8)
-#define CRF_CE(i, j)                           \
-    {                                          \
-        const uint32_t lo_ = a[i], hi_ = a[j]; \
-        a[i] = lo_ < hi_ ? lo_ : hi_;          \
-        a[j] = lo_ < hi_ ? hi_ : lo_;          \
-    }
-#define CRF_SORTNET32(NN)                                                        \
-    template <>                                                                  \
-    struct SortNet32<NN> {                                                       \
-        static __device__ __forceinline__ void sort(uint32_t (&a)[NN]);          \
-    };
-CRF_SORTNET32(40)
-CRF_SORTNET32(56)
-CRF_SORTNET32(72)
-CRF_SORTNET32(88)
-CRF_SORTNET32(104)
-CRF_SORTNET32(120)
-#undef CRF_SORTNET32
-__device__ __forceinline__ void SortNet32<40>::sort(uint32_t (&a)[40]) {
-#define CRF_SORTNET_N 40
-#include "sortnet.inc"
-}
-__device__ __forceinline__ void SortNet32<56>::sort(uint32_t (&a)[56]) {
-#define CRF_SORTNET_N 56
-#include "sortnet.inc"
-}
-__device__ __forceinline__ void SortNet32<72>::sort(uint32_t (&a)[72]) {
-#define CRF_SORTNET_N 72
-#include "sortnet.inc"
-}
-__device__ __forceinline__ void SortNet32<88>::sort(uint32_t (&a)[88]) {
-#define CRF_SORTNET_N 88
-#include "sortnet.inc"
-}
-__device__ __forceinline__ void SortNet32<104>::sort(uint32_t (&a)[104]) {
-#define CRF_SORTNET_N 104
-#include "sortnet.inc"
-}
-__device__ __forceinline__ void SortNet32<120>::sort(uint32_t (&a)[120]) {
-#define CRF_SORTNET_N 120
-#include "sortnet.inc"
-}
-#undef CRF_CE
 
 // ---------------------------------------------------------------------------------------------------------------
 // 65..128 members, ONE sorting network over 32-bit composites (r03).  The split kernel above sorts two chunks of 64-bit
@@ -1514,8 +1456,6 @@ hipError_t launch_plan(const RankPlan<P>& plan, const float* const* d_members, c
     if (info) info->kernel_name = plan.name;
     return hipGetLastError();
 }
-
-int pad_pow2(int cs) { return cs <= 8 ? 8 : cs <= 16 ? 16 : cs <= 32 ? 32 : cs <= 64 ? 64 : 128; }
 
 }  // namespace
 
