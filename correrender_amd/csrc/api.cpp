@@ -138,8 +138,8 @@ int install_narrow_table(crf_context* c) {
     return CRF_OK;
 }
 
-// Members in a narrow native format: the fp32 copy that every kernel reads but the native Pearson and Kendall fields, the
-// native sibling reductions, the extrema and the reference gathers -- one owned block plus the member table, converted on
+// Members in a narrow native format: the fp32 copy that every kernel reads but the native Pearson, Kendall and binned-MI
+// fields, the native sibling reductions, the extrema and the reference gathers -- one owned block plus the member table, converted on
 // stream s at the first call that needs it (a user of those entry points alone never pays for it).  Dropped with the packed copy (drop_wide).
 int ensure_wide(crf_context* c, hipStream_t s) {
     if (c->format == CRF_MEMBER_F32 || !c->members.empty()) return CRF_OK;
@@ -179,8 +179,21 @@ bool native_kendall(const crf_context* c, const crf_params* p) {
            c->cs <= crf::kNarrowMaxMembers && c->narrow_element_aligned && !c->windowed;
 }
 
+// The binned-MI field reads them the same way (kernels_binned_narrow.hip: mi_binned_narrow_kernel) at the member counts of
+// the sort-based kernel; the histogram kernel (129+ members, CRF_BINNED_HIST=1) stays on the copy.
+// Routing by measurement (crf_internal.h: binned_narrow_routed; profiles/narrow_binned_ab.md): uint8 at every member
+// count, uint16 at 17..32 and 49..64 members, float16 at 49..64; the rest was not faster than the copy route and stays on it.
+bool native_binned(const crf_context* c, const crf_params* p) {
+    if (c->format == CRF_MEMBER_F32 || (p->measure != CRF_MI_BINNED && p->measure != CRF_BINNED_MI_CC)) return false;
+    if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1') return false;
+    return !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 && c->cs <= crf::kNarrowMaxMembers &&
+           c->narrow_element_aligned && !c->windowed && crf::binned_narrow_routed(c->format, c->cs);
+}
+
 // the per-voxel kernel of this field evaluation reads the narrow members (c->d_narrow_table), no fp32 copy
-bool native_field(const crf_context* c, const crf_params* p) { return native_pearson(c, p) || native_kendall(c, p); }
+bool native_field(const crf_context* c, const crf_params* p) {
+    return native_pearson(c, p) || native_kendall(c, p) || native_binned(c, p);
+}
 
 // The sibling reductions (ensemble mean / spread, set predicate) read narrow members directly under the same condition
 // (kernels_stats.hip: ensemble_stat_narrow_kernel, set_predicate_narrow_kernel), at any member count.  The extrema and the
@@ -773,6 +786,15 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
             break;
         case CRF_MI_BINNED:
         case CRF_BINNED_MI_CC:
+            if (native) {  // binned MI on narrow members: the reference side is fp32 as ever
+                if ((phase & 1u) && !ref.values) {
+                    CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, ref.voxel, c->d_ref, s));
+                    ref.values = c->d_ref;
+                }
+                e = crf::launch_mi_binned_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, ref, ba, c->d_tables,
+                                                 prep, out, s, e0, e1, info);
+                break;
+            }
             if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1')  // tuning: histogram kernel for any cs
                 e = crf::launch_mi_binned_hist(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s,
                                                e0, e1, info);
@@ -821,7 +843,7 @@ int apply_abs(crf_context* c, const crf_params* p, void* device_out, void* strea
 // first voxel), so that every per-voxel kernel can be launched on a range without knowing about ranges.  Range lengths
 // are multiples of 1024 voxels (4 KiB: every range stays as aligned as the members themselves) and shrink towards the
 // end: the copy of the last range into the caller's buffer is the only host work no kernel hides.
-// native: the tables hold the narrow members' pointers (the native Pearson and Kendall fields), advanced by whole
+// native: the tables hold the narrow members' pointers (the native Pearson, Kendall and binned-MI fields), advanced by whole
 // elements; a range starts at a multiple of 1024 voxels, so they stay as aligned as the members (4 bytes for Pearson, the
 // element for Kendall) and every range but the last is whole dwords.
 int ensure_host_ranges(crf_context* c, bool native) {

@@ -37,14 +37,14 @@ struct crf_context {
     int max_vpt = 1;
     // primary members in a narrow native format (crf_upload_members_format / crf_bind_members_device_format): `narrow`
     // holds the cs device pointers and `members` stays empty until a call that needs fp32 members builds the widened
-    // copy (api.cpp: ensure_wide), one owned block; the Pearson and the Kendall field at 2..128 members, the sibling
+    // copy (api.cpp: ensure_wide), one owned block; the Pearson, the Kendall and (where routed: api.cpp native_binned) the binned-MI field at 2..128 members, the sibling
     // reductions, the extrema and the reference gathers read `narrow` directly
     int format = CRF_MEMBER_F32;
     void* narrow_owned_block = nullptr;
     std::vector<const void*> narrow;
     const void** d_narrow_table = nullptr;
     bool narrow_aligned = false;       // every narrow pointer is 4-byte aligned (the native Pearson kernel loads dwords)
-    bool narrow_element_aligned = false;  // ... aligned to its element (the native Kendall kernel loads elements)
+    bool narrow_element_aligned = false;  // ... aligned to its element (the native Kendall and binned-MI kernels load elements)
     void* wide_block = nullptr;        // the widened copy, lazily
     int last_format = CRF_MEMBER_F32;  // what the per-voxel kernel of the last field evaluation read
     // secondary members (second scalar field of the SEPARATE / SEPARATE_SYMMETRIC modes), optional

@@ -3,17 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "crf_binned_bins.h"  // bin_index_x86 and the per-sample bin of binned MI (host-usable)
 #include "crf_internal.h"
 
 namespace crf {
-
-// int(t) the way the reference's x86-64 build evaluates a bin index before clamping it to [0, numBins - 1]
-// (MutualInformation.cpp:66-67): cvttsd2si yields INT_MIN for NaN and for every t outside the int range -- so a POSITIVE
-// overflow (t >= 2^31: caller-supplied extrema far narrower than the data, or +inf data) lands in bin 0, where the
-// GPU's saturating conversion would give INT_MAX and bin numBins - 1.  Negative overflow and NaN saturate to values
-// that clamp to bin 0 either way, so one compare suffices.
-__device__ __forceinline__ int bin_index_x86(double t) { return t < 2147483648.0 ? int(t) : 0; }
-
 
 // Streaming member loads through buffer descriptors.  Member base pointers come out of a pointer table, so plain
 // loads are flat/global loads with a 64-bit VGPR address each (two VGPRs + a 64-bit VALU add per load in flight).  A
@@ -41,6 +34,17 @@ __device__ __forceinline__ float load_member_cached(const float* base, uint32_t 
 }
 __device__ __forceinline__ float load_member_nt(const float* base, uint32_t bytes, uint32_t byte_offset) {
     return buffer_load_f32_nt(make_member_rsrc(base, bytes), byte_offset);
+}
+// One stored element of a member in a narrow native format, zero-extended: a byte / short buffer load (non-temporal like
+// load_member_nt; the hardware bounds check makes an offset at or past `bytes` read 0 without a memory request).
+// Sub-dword loads ask for nothing but the element's own alignment.
+template <int FMT>
+__device__ __forceinline__ uint32_t load_code_nt(const void* base, uint32_t bytes, uint32_t byte_offset) {
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), /*stride*/ short(0), int(bytes), 0x00020000);
+    if constexpr (FMT == CRF_MEMBER_U8)
+        return __builtin_amdgcn_raw_buffer_load_b8(rsrc, int(byte_offset), 0, kAuxNonTemporal);
+    else
+        return __builtin_amdgcn_raw_buffer_load_b16(rsrc, int(byte_offset), 0, kAuxNonTemporal);
 }
 // Result stores of the bandwidth-bound kernels: written once, never re-read by the kernel (non-temporal)
 __device__ __forceinline__ void store_result_nt(float* p, float v) { __builtin_nontemporal_store(v, p); }

@@ -157,10 +157,11 @@ hipError_t launch_pack_members(const float* const* d_members, int cs, size_t num
                                unsigned char* body, uint32_t* d_fallbacks, hipStream_t s);
 // ---- narrow primary members (include/corrfield.h: crf_member_format) ---------------------------------------------
 // The value the calculators see of a u8 / u16 / f16 element is float(b) / 255.0f, float(s) / 65535.0f, float(h)
-// (reference: src/Volume/Cache/HostCacheEntry.cpp:107-176).  The Pearson and the Kendall field at 2..kNarrowMaxMembers
-// members read such members directly (kernels_pearson.hip: pearson_narrow_kernel; kernels_rank_narrow.hip:
-// kendall_narrow_kernel), and so do the sibling reductions, the extrema and the gathers; everything else runs on an fp32
-// copy that launch_widen_members builds (kernels_common.hip).
+// (reference: src/Volume/Cache/HostCacheEntry.cpp:107-176).  The Pearson, the Kendall and the binned-MI field at
+// 2..kNarrowMaxMembers members read such members directly (kernels_pearson.hip: pearson_narrow_kernel;
+// kernels_rank_narrow.hip: kendall_narrow_kernel; kernels_binned_narrow.hip: mi_binned_narrow_kernel), and so do the
+// sibling reductions, the extrema and the gathers; everything else runs on an fp32 copy that launch_widen_members builds
+// (kernels_common.hip).
 constexpr int kNarrowMaxMembers = 128;
 // A narrow member must be smaller than this: the native kernel's 32-bit voxel index and byte offset of the last block's
 // surplus lanes (up to 1020 voxels past the end) must not wrap.
@@ -227,6 +228,24 @@ hipError_t launch_mi_binned(const float* const* d_members, int cs, size_t num_vo
 hipError_t launch_mi_binned_hist(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                                  const BinnedArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
                                  hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
+// ---- kernels_binned_narrow.hip: binned MI on narrow members, read as stored ----------------------------------------
+// 2 <= cs <= kNarrowMaxMembers, bit-identical to launch_mi_binned on the converted values.  d_narrow: cs device pointers to
+// num_voxels elements of `format`, each aligned to its element (no more); num_voxels x element size below kNarrowMaxBytes.
+// ref.values holds the cs reference values (fp32, any values) when ref.prepare(); d_prep gets launch_binned_prep's layout
+// with the stride of launch_mi_binned (cs rounded up to 16).
+// Which (format, member count) the native kernel serves, by measurement (profiles/narrow_binned_ab.md: native kernel time
+// <= the fp32 kernel's on the copy + its run-to-run spread, per format and N = cs rounded up to 16): uint8 (table front
+// end) at every N; uint16 at N = 32 and 64; float16 at N = 64.  The 16-bit formats at 100 and 128 members and float16 at 24
+// were 2-4 % slower than the copy route and stay on it, as do the 16-bit N that were not measured (16, 48, 80, 96); only
+// the routed instantiations are built.
+inline bool binned_narrow_routed(int format, int cs) {
+    const int n = (cs + 15) / 16 * 16;
+    return format == CRF_MEMBER_U8 || (format == CRF_MEMBER_U16 && (n == 32 || n == 64)) ||
+           (format == CRF_MEMBER_F16 && n == 64);
+}
+hipError_t launch_mi_binned_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, const RefSource& ref,
+                                   const BinnedArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
+                                   hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 struct KraskovArgs {
     int k;
     int estimator;  // 1 or 2

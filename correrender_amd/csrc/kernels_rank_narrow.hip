@@ -18,18 +18,7 @@
 
 namespace crf {
 
-// One stored element, zero-extended: a byte / short buffer load (non-temporal like load_member_nt; the hardware bounds
-// check makes an offset at or past `bytes` read 0 without a memory request).  Sub-dword loads ask for nothing but the
-// element's own alignment.
-template <int FMT>
-__device__ __forceinline__ uint32_t load_code_nt(const void* base, uint32_t bytes, uint32_t byte_offset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), /*stride*/ short(0), int(bytes), 0x00020000);
-    if constexpr (FMT == CRF_MEMBER_U8)
-        return __builtin_amdgcn_raw_buffer_load_b8(rsrc, int(byte_offset), 0, kAuxNonTemporal);
-    else
-        return __builtin_amdgcn_raw_buffer_load_b16(rsrc, int(byte_offset), 0, kAuxNonTemporal);
-}
-
+// (one stored element per load: load_code_nt, crf_device.h)
 // The front end a rank kernel over narrow members needs: a[p] = the voxel's (key, slot) composites in ascending order.
 // Slot e holds member perm[e] (PERMUTED) or member e.  N - 8 < cs <= N: the first N - 8 slots are members whatever cs is
 // and carry no guard; a slot past cs loads at kOutOfRangeOffset and gets the pad key, so the pads end up behind the cs

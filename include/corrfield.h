@@ -155,18 +155,24 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *     asks for the element's own alignment only (2 bytes for the 16-bit formats, none for uint8).  The reference side
  *     -- a reference point, a caller's host or device vector, CRF_FLAG_REFERENCE_FROM_SECONDARY, prepared slots --
  *     stays fp32 with any values.
+ *   - The binned mutual-information field (CRF_MI_BINNED, CRF_BINNED_MI_CC without CRF_FLAG_SYMMETRIC) reads the narrow
+ *     members directly where that was measured to be no slower than the copy route -- uint8 at 2..128 members, uint16 at
+ *     17..32 and 49..64, float16 at 49..64; other counts take the fp32 copy -- (mi_binned_narrow_kernel: one byte / short load per member; a uint8 code
+ *     becomes its bin through a 256-entry table that each block fills from min_query, max_query and num_bins, a 16-bit
+ *     code through the arithmetic of the fp32 kernel on its value); crf_last_member_format then returns the narrow
+ *     format.  Alignment and reference side as for the Kendall field.
  *   - The sibling reductions (crf_compute_ensemble_stat[_device], crf_compute_set_predicate[_device]) read the narrow
  *     members directly at any member count (ensemble_stat_narrow_kernel, set_predicate_narrow_kernel, reported by
  *     crf_last_kernel_name; crf_last_member_format speaks of field evaluations only and is left alone).  Like the
  *     Pearson field they load whole dwords, so borrowed members that are not all 4-byte aligned take the fp32 copy.
  *   - crf_member_minmax and the reference gathers (crf_gather_reference, crf_gather_reference_device,
  *     crf_gather_reference_rows_device) read the narrow members directly, whatever their alignment.
- *   - Everything else -- Spearman, the mutual-information, DKL, symmetric and pair-request evaluations, and the Pearson
- *     and Kendall fields above 128 members -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
+ *   - Everything else -- Spearman, Kraskov mutual information, DKL, symmetric and pair-request evaluations, and the
+ *     Pearson, Kendall and binned-MI fields above 128 members (binned MI also at the counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
  *     call that needs it (one owned block of cs x xs*ys*zs floats; CRF_ERR_DEVICE naming the copy and its size if it
  *     cannot be allocated) and drops in crf_set_grid, upload, bind and crf_members_changed; crf_last_member_format then
  *     returns CRF_MEMBER_F32.  So do the Pearson field and the sibling reductions over borrowed members that are not all
- *     4-byte aligned.  A context that only runs the entry points of the four items above never builds the copy;
+ *     4-byte aligned.  A context that only runs the entry points of the five items above never builds the copy;
  *     crf_wide_copy_bytes tells.
  *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.  Secondary members are fp32 only.
  *     crf_group_* evaluations on a context that holds narrow members: CRF_ERR_UNSUPPORTED.
@@ -181,11 +187,11 @@ enum crf_member_format { /* a tag only: the function crf_member_format() below s
 int crf_upload_members_format(crf_context* ctx, int format, const void* const* host_members);
 int crf_bind_members_device_format(crf_context* ctx, int format, const void* const* device_members);
 int crf_member_format(const crf_context* ctx);      /* format of the bound primary members */
-/* format the per-voxel kernel of the last field evaluation read: the members' own after a native Pearson or Kendall
- * field, CRF_MEMBER_F32 after anything that ran on fp32 members or on the fp32 copy */
+/* format the per-voxel kernel of the last field evaluation read: the members' own after a native Pearson, Kendall
+ * or binned-MI field, CRF_MEMBER_F32 after anything that ran on fp32 members or on the fp32 copy */
 int crf_last_member_format(const crf_context* ctx);
-/* bytes of the fp32 copy of narrow members held right now; 0 if none or ctx == NULL (the native Pearson and Kendall
- * fields, the sibling reductions, the extrema and the gathers never build it) */
+/* bytes of the fp32 copy of narrow members held right now; 0 if none or ctx == NULL (the native Pearson, Kendall and
+ * binned-MI fields, the sibling reductions, the extrema and the gathers never build it) */
 size_t crf_wide_copy_bytes(const crf_context* ctx);
 /* min of per-member minima / max of per-member maxima over the local grid (CorrelationCalculator.cpp:822-829 on
  * top of VolumeData::getMinMaxScalarFieldValue, VolumeData.cpp:1632-1670); computed on the device, cached until
