@@ -190,9 +190,22 @@ bool native_binned(const crf_context* c, const crf_params* p) {
            c->narrow_element_aligned && !c->windowed && crf::binned_narrow_routed(c->format, c->cs);
 }
 
-// the per-voxel kernel of this field evaluation reads the narrow members (c->d_narrow_table), no fp32 copy
+// The Spearman field does too at 33..128 members (kernels_rank_narrow.hip: spearman_narrow_kernel), where the fp32 route
+// would defer every voxel with two equal values to a list pass; up to 32 members the fp32 kernels handle ties in line and
+// the call stays on the copy.  Routing by measurement (crf_internal.h: spearman_narrow_routed;
+// profiles/narrow_spearman_ab.md).  CRF_RANK_U32 selects among the fp32 kernels only: it does not move a native call.
+bool native_spearman(const crf_context* c, const crf_params* p) {
+    return c->format != CRF_MEMBER_F32 && p->measure == CRF_SPEARMAN && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 33 &&
+           c->cs <= crf::kNarrowMaxMembers && c->narrow_element_aligned && !c->windowed &&
+           crf::spearman_narrow_routed(c->format, c->cs);
+}
+
+// The per-voxel kernel of this field evaluation reads the narrow members (c->d_narrow_table), no fp32 copy: the Pearson,
+// Kendall and binned-MI fields at 2..128 members and the Spearman field at 33..128, each under its own conditions above.
+// Everything else -- Spearman up to 32 members, Kraskov MI, 129 members and more, the symmetric mode, pair requests,
+// windowed grids -- runs on the fp32 copy (ensure_wide).
 bool native_field(const crf_context* c, const crf_params* p) {
-    return native_pearson(c, p) || native_kendall(c, p) || native_binned(c, p);
+    return native_pearson(c, p) || native_kendall(c, p) || native_spearman(c, p) || native_binned(c, p);
 }
 
 // The sibling reductions (ensemble mean / spread, set predicate) read narrow members directly under the same condition
@@ -770,13 +783,13 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
         }
         case CRF_SPEARMAN:
         case CRF_KENDALL:
-            if (native) {  // Kendall on narrow members: one pass, no todo list; the reference side is fp32 as ever
+            if (native) {  // on narrow members: one pass, no todo list; the reference side is fp32 as ever
                 if ((phase & 1u) && !ref.values) {
                     CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, ref.voxel, c->d_ref, s));
                     ref.values = c->d_ref;
                 }
-                e = crf::launch_kendall_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, ref, prep, out, s, e0, e1,
-                                               info);
+                e = (p->measure == CRF_SPEARMAN ? crf::launch_spearman_narrow : crf::launch_kendall_narrow)(
+                    c->d_narrow_table, c->format, c->cs, c->num_voxels, ref, prep, out, s, e0, e1, info);
                 break;
             }
             if (c->cs > 16)
@@ -843,9 +856,9 @@ int apply_abs(crf_context* c, const crf_params* p, void* device_out, void* strea
 // first voxel), so that every per-voxel kernel can be launched on a range without knowing about ranges.  Range lengths
 // are multiples of 1024 voxels (4 KiB: every range stays as aligned as the members themselves) and shrink towards the
 // end: the copy of the last range into the caller's buffer is the only host work no kernel hides.
-// native: the tables hold the narrow members' pointers (the native Pearson, Kendall and binned-MI fields), advanced by whole
-// elements; a range starts at a multiple of 1024 voxels, so they stay as aligned as the members (4 bytes for Pearson, the
-// element for Kendall) and every range but the last is whole dwords.
+// native: the tables hold the narrow members' pointers (the native Pearson, Kendall, Spearman and binned-MI fields), advanced
+// by whole elements; a range starts at a multiple of 1024 voxels, so they stay as aligned as the members (4 bytes for
+// Pearson, the element for the others) and every range but the last is whole dwords.
 int ensure_host_ranges(crf_context* c, bool native) {
     if (c->host_chunks > 0 && c->chunk_native == native) return CRF_OK;
     c->host_chunks = 0;

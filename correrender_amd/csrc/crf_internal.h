@@ -210,6 +210,19 @@ constexpr int pad_pow2(int cs) { return cs <= 8 ? 8 : cs <= 16 ? 16 : cs <= 32 ?
 hipError_t launch_kendall_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, const RefSource& ref,
                                  float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
                                  LaunchInfo* info);
+// Spearman the same way: one kernel, one pass, ties included (no todo list, no workspace), 33 <= cs <= kNarrowMaxMembers,
+// bit-identical to launch_spearman on the converted values.  d_narrow as for launch_kendall_narrow (element alignment
+// only).  ref.values holds the cs reference values (fp32, any values) when ref.prepare(); d_prep gets
+// launch_spearman_prep's table.  Up to 32 members stay on the fp32 copy (the fp32 kernels handle ties in line there).
+// Which (format, member count) the native kernel serves, by measurement (profiles/narrow_spearman_ab.md: native kernel
+// time <= the fp32 kernels' on the copy + their run-to-run spread, per format and N = cs rounded up to 8): every format
+// at every N from 40 to 128.  hipErrorInvalidValue for a combination that is not routed.
+inline bool spearman_narrow_routed(int format, int cs) {
+    return format != CRF_MEMBER_F32 && cs >= 33 && cs <= kNarrowMaxMembers;
+}
+hipError_t launch_spearman_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, const RefSource& ref,
+                                  float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
+                                  LaunchInfo* info);
 
 // ---- kernels_binned.hip / kernels_kraskov.hip -------------------------------------------------------------------
 struct BinnedArgs {

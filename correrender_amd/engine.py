@@ -123,8 +123,9 @@ class CorrField:
         a plain [cs, n] uint8 or 16-bit tensor do only when n * itemsize is a multiple of 4.  Otherwise every per-voxel
         evaluation, the Pearson field, ensemble_stat and set_predicate included, runs on the fp32 copy (cs * n floats of
         device memory; last_member_format() says "f32", wide_copy_bytes() its size) -- pad the row stride, or use
-        upload_members, whose copy is aligned.  The native Kendall and binned-MI fields (2..128 members; binned MI: uint8 at any of these counts, uint16 at
-        17..32 and 49..64, float16 at 49..64, else the copy) load single elements and
+        upload_members, whose copy is aligned.  The native Kendall, Spearman and binned-MI fields (2..128 members; Spearman:
+        33..128; binned MI: uint8 at any of these counts, uint16 at 17..32 and 49..64, float16 at 49..64, else the copy)
+        load single elements and
         ask for the element's own alignment only, which every torch tensor has; member_minmax and the reference gathers
         need no alignment."""
         tensors = [members[i] for i in range(self.cs)]

@@ -155,6 +155,10 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *     asks for the element's own alignment only (2 bytes for the 16-bit formats, none for uint8).  The reference side
  *     -- a reference point, a caller's host or device vector, CRF_FLAG_REFERENCE_FROM_SECONDARY, prepared slots --
  *     stays fp32 with any values.
+ *   - The Spearman field (CRF_SPEARMAN without CRF_FLAG_SYMMETRIC) at 33..128 members reads the narrow members directly
+ *     (spearman_narrow_kernel: the same sorted keys, fractional ranks of tie runs in line, no list of deferred voxels,
+ *     whatever CRF_RANK_U32 says); crf_last_member_format then returns the narrow format.  Alignment and reference side
+ *     as for the Kendall field.  At 2..32 members it takes the fp32 copy.
  *   - The binned mutual-information field (CRF_MI_BINNED, CRF_BINNED_MI_CC without CRF_FLAG_SYMMETRIC) reads the narrow
  *     members directly where that was measured to be no slower than the copy route -- uint8 at 2..128 members, uint16 at
  *     17..32 and 49..64, float16 at 49..64; other counts take the fp32 copy -- (mi_binned_narrow_kernel: one byte / short load per member; a uint8 code
@@ -167,12 +171,12 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *     Pearson field they load whole dwords, so borrowed members that are not all 4-byte aligned take the fp32 copy.
  *   - crf_member_minmax and the reference gathers (crf_gather_reference, crf_gather_reference_device,
  *     crf_gather_reference_rows_device) read the narrow members directly, whatever their alignment.
- *   - Everything else -- Spearman, Kraskov mutual information, DKL, symmetric and pair-request evaluations, and the
- *     Pearson, Kendall and binned-MI fields above 128 members (binned MI also at the counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
+ *   - Everything else -- Spearman at 2..32 members, Kraskov mutual information, DKL, symmetric and pair-request evaluations, and the
+ *     Pearson, Spearman, Kendall and binned-MI fields above 128 members (binned MI also at the counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
  *     call that needs it (one owned block of cs x xs*ys*zs floats; CRF_ERR_DEVICE naming the copy and its size if it
  *     cannot be allocated) and drops in crf_set_grid, upload, bind and crf_members_changed; crf_last_member_format then
  *     returns CRF_MEMBER_F32.  So do the Pearson field and the sibling reductions over borrowed members that are not all
- *     4-byte aligned.  A context that only runs the entry points of the five items above never builds the copy;
+ *     4-byte aligned.  A context that only runs the entry points of the six items above never builds the copy;
  *     crf_wide_copy_bytes tells.
  *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.  Secondary members are fp32 only.
  *     crf_group_* evaluations on a context that holds narrow members: CRF_ERR_UNSUPPORTED.
