@@ -59,160 +59,200 @@ int bind_device(crf_context* c) {
     return CRF_OK;
 }
 
-// the packed copy of the members (crf_internal.h); decided again at the next Pearson field evaluation
-void drop_packed(crf_context* c) {
-    if (c->d_packed) (void)hipFree(c->d_packed);
-    c->d_packed = nullptr;
-    c->packed_bytes = 0;
-    c->pack_state = 0;
-}
-
-// the fp32 copy of members in a narrow native format (crf_context.h); built again by the next call that needs it
-void drop_wide(crf_context* c) {
-    if (c->format == CRF_MEMBER_F32) return;
-    if (c->wide_block) (void)hipFree(c->wide_block);
-    c->wide_block = nullptr;
-    c->members.clear();
-    c->minmax_valid = false;
-    c->host_chunks = 0;
-    c->windows = 0;
-}
-
-void release_members(crf_context* c) {
-    drop_wide(c);
-    if (c->owned_block) (void)hipFree(c->owned_block);
-    c->owned_block = nullptr;
-    if (c->narrow_owned_block) (void)hipFree(c->narrow_owned_block);
-    c->narrow_owned_block = nullptr;
-    c->narrow.clear();
-    c->format = CRF_MEMBER_F32;
-    c->members.clear();
-    c->minmax_valid = false;
-    drop_packed(c);
-}
-
-void release_secondary(crf_context* c) {
-    if (c->sec_owned_block) (void)hipFree(c->sec_owned_block);
-    c->sec_owned_block = nullptr;
-    c->sec_members.clear();
-    c->sec_minmax_valid = false;
-}
-
 int alignment_vpt(const void* p) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p);
     return (a & 15u) == 0 ? 4 : ((a & 7u) == 0 ? 2 : 1);
-}
-
-int install_member_table(crf_context* c) {
-    int vpt = 4;
-    for (const float* p : c->members) vpt = std::min(vpt, alignment_vpt(p));
-    c->max_vpt = vpt;
-    CRF_HIP(c, hipMemcpyAsync(c->d_member_table, c->members.data(), sizeof(float*) * size_t(c->cs),
-                              hipMemcpyHostToDevice, c->stream));
-    CRF_HIP(c, hipStreamSynchronize(c->stream));
-    c->minmax_valid = false;
-    c->host_chunks = 0;  // the per-range pointer tables of the host-output path describe the old members
-    c->windows = 0;      // ... and so do the window tables of a >= 4 GiB grid
-    drop_packed(c);      // ... and the packed copy their values
-    return CRF_OK;
 }
 
 const char* format_name(int format) {
     return format == CRF_MEMBER_U8 ? "u8" : format == CRF_MEMBER_U16 ? "u16" : format == CRF_MEMBER_F16 ? "f16" : "f32";
 }
 
-int install_narrow_table(crf_context* c) {
-    c->narrow_aligned = c->narrow_element_aligned = true;
-    const uintptr_t element_mask = crf::member_format_bytes(c->format) - 1;
-    for (const void* p : c->narrow) {
-        c->narrow_aligned = c->narrow_aligned && (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
-        c->narrow_element_aligned = c->narrow_element_aligned && (reinterpret_cast<uintptr_t>(p) & element_mask) == 0;
+// what a launch on the whole local grid reads
+crf_launch_view whole_view(const crf_context* c) {
+    const crf_grid_state& g = c->grid;
+    return {g.members.f32_table(), g.secondary.f32_table(), g.narrow.table.get(), c->alloc_voxels, g.members.vpt, 0};
+}
+
+// ---- what is derived from the members, and what drops it ---------------------------------------------------------------
+//   derived object                         built by             reads
+//   min/max cache of a set                 member_minmax        the set's values
+//   host range tables (chunk_tables)       ensure_host_ranges   the pointers of `members` or of `narrow`
+//   window tables                          ensure_windows       the pointers of `members` and of `secondary`
+//   packed copy                            ensure_packed        the values of `members`
+//   wide copy (`members` of narrow ones)   ensure_wide          the values of `narrow`
+// Each function below is the whole answer to "what goes when this changes"; crf_set_grid drops everything by replacing
+// the grid state.
+
+// the packed copy; decided again at the next Pearson field evaluation (also when the layout policy changes)
+void drop_packed(crf_context* c) {
+    c->grid.packed.reset();
+    c->grid.pack_state = 0;
+}
+
+// The fp32 view of narrow members appeared (ensure_wide): tables built while it was missing do not point into it.  The
+// min/max cache stays: it holds the extrema of the narrow values, and the copy holds the same values.
+void fp32_view_appeared(crf_context* c) {
+    c->grid.host_chunks = 0;
+    c->grid.windows = 0;
+}
+
+// The primary members were replaced (upload, bind) or overwritten in place (crf_members_changed).
+void primary_members_changed(crf_context* c) {
+    crf_grid_state& g = c->grid;
+    g.members.minmax_valid = g.narrow.minmax_valid = false;
+    g.host_chunks = 0;
+    g.windows = 0;
+    drop_packed(c);
+    if (g.format != CRF_MEMBER_F32) {  // the wide copy, and the fp32 pointers into it
+        g.wide.reset();
+        g.members.ptrs.clear();
     }
-    CRF_HIP(c, hipMemcpyAsync(c->d_narrow_table, c->narrow.data(), sizeof(void*) * size_t(c->cs), hipMemcpyHostToDevice,
+}
+
+void secondary_members_changed(crf_context* c) {
+    c->grid.secondary.minmax_valid = false;
+    c->grid.windows = 0;
+}
+
+// the set's alignment facts and its device table, from set.ptrs
+int install_table(crf_context* c, crf_member_set& set) {
+    const uintptr_t element_mask = crf::member_format_bytes(set.format) - 1;
+    set.vpt = 4;
+    set.dword_aligned = set.element_aligned = true;
+    for (const void* p : set.ptrs) {
+        set.vpt = std::min(set.vpt, alignment_vpt(p));
+        set.dword_aligned = set.dword_aligned && (reinterpret_cast<uintptr_t>(p) & 3u) == 0;
+        set.element_aligned = set.element_aligned && (reinterpret_cast<uintptr_t>(p) & element_mask) == 0;
+    }
+    CRF_HIP(c, set.table.reserve(size_t(c->cs)));
+    CRF_HIP(c, hipMemcpyAsync(set.table.get(), set.ptrs.data(), sizeof(void*) * size_t(c->cs), hipMemcpyHostToDevice,
                               c->stream));
     CRF_HIP(c, hipStreamSynchronize(c->stream));
-    c->minmax_valid = false;
-    c->host_chunks = 0;
-    c->windows = 0;
-    drop_packed(c);
+    c->view = whole_view(c);
     return CRF_OK;
 }
 
-// Members in a narrow native format: the fp32 copy that every kernel reads but the native Pearson, Kendall and binned-MI
-// fields, the native sibling reductions, the extrema and the reference gathers -- one owned block plus the member table, converted on
-// stream s at the first call that needs it (a user of those entry points alone never pays for it).  Dropped with the packed copy (drop_wide).
+// Replaces the primary members (secondary == false; any format) or the secondary ones (fp32) by cs volumes uploaded from
+// host memory into one owned block, or bound where they lie in device memory.  label: how the messages name a member.
+int set_members(crf_context* c, bool secondary, int format, const void* const* members, bool upload, const char* label) {
+    if (!c || !members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (format < CRF_MEMBER_F32 || format > CRF_MEMBER_F16)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("unknown member format %d", format));
+    if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
+    for (int i = 0; i < c->cs; i++)
+        if (!members[i]) return fail(c, CRF_ERR_ARGUMENT, fmt("%s %d is a null pointer", label, i));
+    // the native kernels address a member with 32-bit byte offsets (crf_internal.h: kNarrowMaxBytes, just under 4 GiB)
+    if (format != CRF_MEMBER_F32 && c->alloc_voxels * crf::member_format_bytes(format) >= crf::kNarrowMaxBytes)
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%s members of 4 GiB or more are not supported (%zu voxels per member)",
+                                                format_name(format), c->alloc_voxels));
+    if (int r = bind_device(c)) return r;
+    crf_grid_state& g = c->grid;
+    if (secondary) {
+        secondary_members_changed(c);
+        g.secondary.clear();
+    } else {
+        primary_members_changed(c);
+        g.members.clear();
+        g.narrow.clear();
+        g.format = format;
+    }
+    crf_member_set& set = secondary ? g.secondary : format == CRF_MEMBER_F32 ? g.members : g.narrow;
+    set.format = format;
+    if (!upload) {
+        set.ptrs.assign(members, members + c->cs);
+        return install_table(c, set);
+    }
+    // every member starts 256-byte aligned (wide vector loads)
+    const size_t bytes = c->alloc_voxels * crf::member_format_bytes(format);
+    const size_t stride = (bytes + 255) & ~size_t(255);
+    CRF_HIP(c, set.owned.reserve(stride * size_t(c->cs)));
+    for (int i = 0; i < c->cs; i++) {
+        set.ptrs.push_back(set.owned.get() + stride * size_t(i));
+        CRF_HIP(c, hipMemcpyAsync(set.owned.get() + stride * size_t(i), members[i], bytes, hipMemcpyHostToDevice,
+                                  c->stream));
+    }
+    return install_table(c, set);
+}
+
+// The extrema of a set's values, computed once per set of values.
+int member_minmax(crf_context* c, crf_member_set& set, float* out_min, float* out_max) {
+    if (!out_min || !out_max) return fail(c, CRF_ERR_ARGUMENT, "null output");
+    if (!set.minmax_valid) {
+        if (int r = bind_device(c)) return r;
+        uint32_t* d_keys = c->minmax.get();
+        if (set.format != CRF_MEMBER_F32)  // the narrow members as stored: no fp32 copy
+            CRF_HIP(c, crf::launch_minmax_narrow(set.table.get(), set.format, c->cs, c->alloc_voxels, d_keys, c->stream));
+        else
+            CRF_HIP(c, crf::launch_minmax(set.f32_table(), c->cs, c->alloc_voxels, d_keys, c->stream));
+        uint32_t keys[2];
+        CRF_HIP(c, hipMemcpyAsync(keys, d_keys, sizeof keys, hipMemcpyDeviceToHost, c->stream));
+        CRF_HIP(c, hipStreamSynchronize(c->stream));
+        set.min_v = crf::minmax_key_to_float(keys[0]);
+        set.max_v = crf::minmax_key_to_float(keys[1]);
+        set.minmax_valid = true;
+    }
+    *out_min = set.min_v;
+    *out_max = set.max_v;
+    return CRF_OK;
+}
+
+// Narrow members: the fp32 copy for every evaluation without a native route (native_field, native_reduction) -- one owned
+// block that `members` points into, converted on stream s at the first call that needs it.  A caller that stays on the
+// native routes, the extrema and the reference gathers never pays for it.  Dropped with the members it was made from.
 int ensure_wide(crf_context* c, hipStream_t s) {
-    if (c->format == CRF_MEMBER_F32 || !c->members.empty()) return CRF_OK;
+    crf_grid_state& g = c->grid;
+    if (g.format == CRF_MEMBER_F32 || !g.members.ptrs.empty()) return CRF_OK;
     if (int r = bind_device(c)) return r;
     const size_t stride = (c->alloc_voxels + 63) & ~size_t(63);
-    const size_t bytes = stride * sizeof(float) * size_t(c->cs);
-    if (!c->wide_block && hipMalloc(&c->wide_block, bytes) != hipSuccess) {
+    if (g.wide.reserve(stride * size_t(c->cs)) != hipSuccess) {
         (void)hipGetLastError();
-        c->wide_block = nullptr;
         return fail(c, CRF_ERR_DEVICE, fmt("no device memory for the fp32 copy of the %s members (%zu bytes)",
-                                           format_name(c->format), bytes));
+                                           format_name(g.format), stride * sizeof(float) * size_t(c->cs)));
     }
-    CRF_HIP(c, crf::launch_widen_members(c->d_narrow_table, c->format, c->cs, c->alloc_voxels,
-                                         static_cast<float*>(c->wide_block), stride, s));
-    c->members.resize(size_t(c->cs));
-    for (int i = 0; i < c->cs; i++) c->members[size_t(i)] = static_cast<const float*>(c->wide_block) + stride * size_t(i);
-    c->max_vpt = 4;
-    CRF_HIP(c, hipMemcpyAsync(c->d_member_table, c->members.data(), sizeof(float*) * size_t(c->cs), hipMemcpyHostToDevice, s));
+    CRF_HIP(c, crf::launch_widen_members(g.narrow.table.get(), g.format, c->cs, c->alloc_voxels, g.wide.get(), stride, s));
+    for (int i = 0; i < c->cs; i++) g.members.ptrs.push_back(g.wide.get() + stride * size_t(i));
+    g.members.vpt = 4;
+    CRF_HIP(c, hipMemcpyAsync(g.members.table.get(), g.members.ptrs.data(), sizeof(void*) * size_t(c->cs),
+                              hipMemcpyHostToDevice, s));
     CRF_HIP(c, hipStreamSynchronize(s));
-    c->minmax_valid = false;
-    c->host_chunks = 0;
-    c->windows = 0;
+    c->view = whole_view(c);
+    fp32_view_appeared(c);
     return CRF_OK;
 }
 
-// The Pearson field reads narrow members directly (kernels_pearson.hip: pearson_narrow_kernel) when its dword loads can:
-// every member pointer 4-byte aligned; else the evaluation takes the fp32 copy like every other one.
-bool native_pearson(const crf_context* c, const crf_params* p) {
-    return c->format != CRF_MEMBER_F32 && p->measure == CRF_PEARSON && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 &&
-           c->cs <= crf::kNarrowMaxMembers && c->narrow_aligned && !c->windowed;
-}
-
-// The Kendall field reads them with one byte / short load per element (kernels_rank_narrow.hip: kendall_narrow_kernel),
-// so it asks for the element's own alignment only.
-bool native_kendall(const crf_context* c, const crf_params* p) {
-    return c->format != CRF_MEMBER_F32 && p->measure == CRF_KENDALL && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 &&
-           c->cs <= crf::kNarrowMaxMembers && c->narrow_element_aligned && !c->windowed;
-}
-
-// The binned-MI field reads them the same way (kernels_binned_narrow.hip: mi_binned_narrow_kernel) at the member counts of
-// the sort-based kernel; the histogram kernel (129+ members, CRF_BINNED_HIST=1) stays on the copy.
-// Routing by measurement (crf_internal.h: binned_narrow_routed; profiles/narrow_binned_ab.md): uint8 at every member
-// count, uint16 at 17..32 and 49..64 members, float16 at 49..64; the rest was not faster than the copy route and stays on it.
-bool native_binned(const crf_context* c, const crf_params* p) {
-    if (c->format == CRF_MEMBER_F32 || (p->measure != CRF_MI_BINNED && p->measure != CRF_BINNED_MI_CC)) return false;
-    if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1') return false;
-    return !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 2 && c->cs <= crf::kNarrowMaxMembers &&
-           c->narrow_element_aligned && !c->windowed && crf::binned_narrow_routed(c->format, c->cs);
-}
-
-// The Spearman field does too at 33..128 members (kernels_rank_narrow.hip: spearman_narrow_kernel), where the fp32 route
-// would defer every voxel with two equal values to a list pass; up to 32 members the fp32 kernels handle ties in line and
-// the call stays on the copy.  Routing by measurement (crf_internal.h: spearman_narrow_routed;
-// profiles/narrow_spearman_ab.md).  CRF_RANK_U32 selects among the fp32 kernels only: it does not move a native call.
-bool native_spearman(const crf_context* c, const crf_params* p) {
-    return c->format != CRF_MEMBER_F32 && p->measure == CRF_SPEARMAN && !(p->flags & CRF_FLAG_SYMMETRIC) && c->cs >= 33 &&
-           c->cs <= crf::kNarrowMaxMembers && c->narrow_element_aligned && !c->windowed &&
-           crf::spearman_narrow_routed(c->format, c->cs);
-}
-
-// The per-voxel kernel of this field evaluation reads the narrow members (c->d_narrow_table), no fp32 copy: the Pearson,
-// Kendall and binned-MI fields at 2..128 members and the Spearman field at 33..128, each under its own conditions above.
-// Everything else -- Spearman up to 32 members, Kraskov MI, 129 members and more, the symmetric mode, pair requests,
-// windowed grids -- runs on the fp32 copy (ensure_wide).
+// Whether the per-voxel kernel of this field evaluation reads the narrow members as they are (view.narrow), no fp32 copy.
+// Everything else -- Kraskov MI, more than kNarrowMaxMembers members, the symmetric mode, windowed grids, pair requests --
+// runs on the fp32 copy (ensure_wide).  Per measure:
+//   Pearson    2..128 members, dword loads: every member 4-byte aligned (kernels_pearson.hip: pearson_narrow_kernel)
+//   Kendall    2..128 members, element loads: the element's own alignment (kernels_rank_narrow.hip)
+//   Spearman   33..128 members (kernels_rank_narrow.hip); up to 32 the fp32 kernels handle ties in line and the call stays
+//              on the copy (crf_internal.h: spearman_narrow_routed; profiles/narrow_spearman_ab.md).  CRF_RANK_U32 selects
+//              among the fp32 kernels only: it does not move a native call.
+//   binned MI  2..128 members where measured faster than the copy route (crf_internal.h: binned_narrow_routed;
+//              profiles/narrow_binned_ab.md); CRF_BINNED_HIST=1 asks for the histogram kernel, which reads fp32
 bool native_field(const crf_context* c, const crf_params* p) {
-    return native_pearson(c, p) || native_kendall(c, p) || native_spearman(c, p) || native_binned(c, p);
+    const crf_grid_state& g = c->grid;
+    if (g.format == CRF_MEMBER_F32 || (p->flags & CRF_FLAG_SYMMETRIC) || c->cs > crf::kNarrowMaxMembers || c->windowed)
+        return false;
+    switch (p->measure) {
+        case CRF_PEARSON: return c->cs >= 2 && g.narrow.dword_aligned;
+        case CRF_KENDALL: return c->cs >= 2 && g.narrow.element_aligned;
+        case CRF_SPEARMAN:
+            return c->cs >= 33 && g.narrow.element_aligned && crf::spearman_narrow_routed(g.format, c->cs);
+        case CRF_MI_BINNED:
+        case CRF_BINNED_MI_CC:
+            if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1') return false;
+            return c->cs >= 2 && g.narrow.element_aligned && crf::binned_narrow_routed(g.format, c->cs);
+        default: return false;
+    }
 }
 
-// The sibling reductions (ensemble mean / spread, set predicate) read narrow members directly under the same condition
+// The sibling reductions (ensemble mean / spread, set predicate) read narrow members with dword loads
 // (kernels_stats.hip: ensemble_stat_narrow_kernel, set_predicate_narrow_kernel), at any member count.  The extrema and the
 // reference gathers read narrow members element by element and ask for nothing but a narrow format.
 bool native_reduction(const crf_context* c) {
-    return c->format != CRF_MEMBER_F32 && c->narrow_aligned && !c->windowed;
+    return c->grid.format != CRF_MEMBER_F32 && c->grid.narrow.dword_aligned && !c->windowed;
 }
 
 // Packs the members for the Pearson field if the layout policy asks for it (include/corrfield.h: crf_member_layout),
@@ -220,16 +260,17 @@ bool native_reduction(const crf_context* c) {
 int ensure_packed(crf_context* c, hipStream_t s, crf::PackedMembers* use) {
     *use = crf::PackedMembers{};
     const int cs = c->cs;
-    if (c->format != CRF_MEMBER_F32) return CRF_OK;  // the packed copy is an fp32 format
+    if (c->grid.format != CRF_MEMBER_F32) return CRF_OK;  // the packed copy is an fp32 format
     if (c->member_layout == CRF_MEMBER_LAYOUT_RAW || cs < crf::kPackMinMembers || cs > crf::kPackMaxMembers ||
-        c->windowed || c->num_voxels != c->alloc_voxels)
+        c->windowed || c->view.num_voxels != c->alloc_voxels)
         return CRF_OK;
     const bool automatic = c->member_layout == CRF_MEMBER_LAYOUT_AUTO;
-    const size_t tiles = (c->num_voxels + 63) / 64;
+    const size_t tiles = (c->view.num_voxels + 63) / 64;
     const size_t header_bytes = (tiles * size_t(crf::pack_slots(cs)) + 255) & ~size_t(255);
-    if (c->pack_state == 0) {
-        c->pack_state = -1;
-        if (automatic && c->num_voxels < (size_t(1) << 20)) return CRF_OK;  // the one-time encode would not pay off
+    crf_grid_state& g = c->grid;
+    if (g.pack_state == 0) {
+        g.pack_state = -1;
+        if (automatic && c->view.num_voxels < (size_t(1) << 20)) return CRF_OK;  // the one-time encode would not pay off
         // padded slots are stored and read: near the bottom of a 16-slot granule the copy moves more than the members
         if (automatic && crf::pack_voxel_bytes(cs) > crf::kPackAutoByteRatio * double(4 * cs + 4)) return CRF_OK;
         const size_t bytes = header_bytes + tiles * size_t(crf::pack_tile_bytes(crf::pack_slots(cs)));
@@ -239,29 +280,27 @@ int ensure_packed(crf_context* c, hipStream_t s, crf::PackedMembers* use) {
             const size_t keep = std::max(size_t(8) << 30, total_b / 10);
             if (free_b < bytes || free_b - bytes < keep) return CRF_OK;
         }
-        if (!c->d_pack_fallbacks)
-            CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_pack_fallbacks), sizeof(uint32_t)));
-        if (hipMalloc(reinterpret_cast<void**>(&c->d_packed), bytes) != hipSuccess) {
+        CRF_HIP(c, c->pack_fallbacks.reserve(1));
+        if (g.packed.reserve(bytes) != hipSuccess) {
             (void)hipGetLastError();
-            c->d_packed = nullptr;
             if (automatic) return CRF_OK;
             return fail(c, CRF_ERR_DEVICE, fmt("no device memory for the packed members (%zu bytes)", bytes));
         }
-        c->packed_bytes = bytes;
-        CRF_HIP(c, hipMemsetAsync(c->d_pack_fallbacks, 0, sizeof(uint32_t), s));
-        CRF_HIP(c, crf::launch_pack_members(c->d_member_table, cs, c->num_voxels, c->d_packed, c->d_packed + header_bytes,
-                                            c->d_pack_fallbacks, s));
+        uint32_t* d_fallbacks = c->pack_fallbacks.get();
+        CRF_HIP(c, hipMemsetAsync(d_fallbacks, 0, sizeof(uint32_t), s));
+        CRF_HIP(c, crf::launch_pack_members(c->view.members, cs, c->view.num_voxels, g.packed.get(),
+                                            g.packed.get() + header_bytes, d_fallbacks, s));
         uint32_t fallbacks = 0;
-        CRF_HIP(c, hipMemcpyAsync(&fallbacks, c->d_pack_fallbacks, sizeof fallbacks, hipMemcpyDeviceToHost, s));
+        CRF_HIP(c, hipMemcpyAsync(&fallbacks, d_fallbacks, sizeof fallbacks, hipMemcpyDeviceToHost, s));
         CRF_HIP(c, hipStreamSynchronize(s));
         if (automatic && double(fallbacks) > 0.05 * double(tiles) * double(cs)) {
             drop_packed(c);
-            c->pack_state = -1;
+            g.pack_state = -1;
             return CRF_OK;
         }
-        c->pack_state = 1;
+        g.pack_state = 1;
     }
-    if (c->pack_state == 1) *use = crf::PackedMembers{c->d_packed, c->d_packed + header_bytes};
+    if (g.pack_state == 1) *use = crf::PackedMembers{g.packed.get(), g.packed.get() + header_bytes};
     return CRF_OK;
 }
 
@@ -317,20 +356,21 @@ double kraskov_c_term(int k, int estimator) {
 
 int check_ready(crf_context* c) {
     if (!c) return CRF_ERR_ARGUMENT;
-    if (c->cs <= 0 || c->num_voxels == 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
-    if (int(c->format == CRF_MEMBER_F32 ? c->members.size() : c->narrow.size()) != c->cs)
+    if (c->cs <= 0 || c->alloc_voxels == 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
+    const crf_member_set& current = c->grid.format == CRF_MEMBER_F32 ? c->grid.members : c->grid.narrow;
+    if (int(current.ptrs.size()) != c->cs)
         return fail(c, CRF_ERR_STATE, "no member volumes uploaded or bound");
     return CRF_OK;
 }
 
-hipEvent_t take_event(crf_context* c) {
+crf::Event take_event(crf_context* c) {  // empty: none could be created
+    crf::Event e;
     if (!c->ev_free.empty()) {
-        hipEvent_t e = c->ev_free.back();
+        e = std::move(c->ev_free.back());
         c->ev_free.pop_back();
-        return e;
+    } else {
+        (void)e.create();
     }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
 }
 
@@ -347,7 +387,7 @@ int launch_status(crf_context* c, hipError_t e) {
 // hipError_t to the ABI status.
 struct TimedLaunch {
     crf_context* c;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    crf::Event e0, e1;
     crf::LaunchInfo info;
     explicit TimedLaunch(crf_context* ctx, bool timed = true) : c(ctx) {
         if (c->profiling && timed) {
@@ -357,7 +397,7 @@ struct TimedLaunch {
     }
     int finish(hipError_t e) {
         c->last_kernel = info.kernel_name ? info.kernel_name : "";
-        if (e0 && e1) c->ev_pending.emplace_back(e0, e1);
+        if (e0 && e1) c->ev_pending.emplace_back(std::move(e0), std::move(e1));
         return launch_status(c, e);
     }
 };
@@ -390,43 +430,20 @@ int check_slots(crf_context* c, int first, int count, bool one = false) {
                     : fmt("slots [%d, %d) outside [0, %d)", first, first + count, CRF_PREPARED_SLOTS));
 }
 
-int install_secondary_table(crf_context* c) {
-    if (!c->d_sec_table)
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_sec_table), sizeof(float*) * size_t(c->cs)));
-    CRF_HIP(c, hipMemcpyAsync(c->d_sec_table, c->sec_members.data(), sizeof(float*) * size_t(c->cs),
-                              hipMemcpyHostToDevice, c->stream));
-    CRF_HIP(c, hipStreamSynchronize(c->stream));
-    c->sec_minmax_valid = false;
-    c->windows = 0;
-    return CRF_OK;
-}
-
 // Scratch that the per-voxel kernels write (crf_context.h: crf_scratch).  Both functions size every set that the
 // evaluation being issued uses: set 0 alone, or both sets under the range pipeline of compute_to_host, whose ranges run on
 // two streams and may not share a list or a workspace slice.  The pipeline issues its reference-side preparation through
 // the same dispatch as its ranges, with pipeline_voxels = its largest range, before the first range is launched: that
 // call sizes everything, and the calls for the ranges find it large enough (no growth, no synchronisation, between ranges).
-void free_scratch(crf_context* c) {
-    for (crf_scratch& sc : c->scratch) {
-        if (sc.todo) (void)hipFree(sc.todo);
-        if (sc.workspace) (void)hipFree(sc.workspace);
-        sc = crf_scratch{};
-    }
-}
-
 // the most voxels one launch of the evaluation being issued covers: what its blockIdx-indexed workspace is sized for
-size_t launch_voxels(const crf_context* c) { return c->pipeline_voxels ? c->pipeline_voxels : c->num_voxels; }
+size_t launch_voxels(const crf_context* c) { return c->pipeline_voxels ? c->pipeline_voxels : c->view.num_voxels; }
 
 int ensure_workspace(crf_context* c, size_t need) {
     for (int set = 0; set < c->pipeline_sets; set++) {
-        crf_scratch& sc = c->scratch[set];
-        if (need <= sc.workspace_bytes) continue;
+        crf_scratch& sc = c->grid.scratch[set];
+        if (need <= sc.workspace.count()) continue;
         CRF_HIP(c, hipDeviceSynchronize());  // an earlier evaluation on a caller stream may still use the old workspace
-        if (sc.workspace) (void)hipFree(sc.workspace);
-        sc.workspace = nullptr;
-        sc.workspace_bytes = 0;
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&sc.workspace), need));
-        sc.workspace_bytes = need;
+        CRF_HIP(c, sc.workspace.reserve(need));
     }
     return CRF_OK;
 }
@@ -435,23 +452,17 @@ int ensure_workspace(crf_context* c, size_t need) {
 // grid (num_voxels == alloc_voxels whenever no NarrowScope is active).  Set 1 only ever holds one range.
 int ensure_todo(crf_context* c) {
     for (int set = 0; set < c->pipeline_sets; set++) {
-        crf_scratch& sc = c->scratch[set];
+        crf_scratch& sc = c->grid.scratch[set];
         const size_t need = set == 0 ? c->alloc_voxels : c->pipeline_voxels;
-        if (need <= sc.todo_voxels) continue;
-        if (sc.todo) {  // another range layout than the one it was sized for
-            CRF_HIP(c, hipDeviceSynchronize());
-            (void)hipFree(sc.todo);
-        }
-        sc.todo = nullptr;
-        sc.todo_voxels = 0;
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&sc.todo), (need + 1) * sizeof(uint32_t)));
-        sc.todo_voxels = need;
+        if (need + 1 <= sc.todo.count()) continue;
+        if (sc.todo) CRF_HIP(c, hipDeviceSynchronize());  // another range layout than the one it was sized for
+        CRF_HIP(c, sc.todo.reserve(need + 1));  // a counter, then `need` indices
     }
     return CRF_OK;
 }
 
 int ensure_out(crf_context* c) {  // device result of the host-output calls
-    if (!c->d_out) CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_out), c->alloc_voxels * sizeof(float)));
+    CRF_HIP(c, c->grid.out.reserve(c->alloc_voxels));
     return CRF_OK;
 }
 
@@ -459,21 +470,20 @@ int ensure_out(crf_context* c) {  // device result of the host-output calls
 constexpr size_t kWindowVoxels = size_t(1) << 29;  // 2 GiB of every member per launch
 
 int ensure_windows(crf_context* c) {
-    if (c->windows > 0) return CRF_OK;
+    crf_grid_state& g = c->grid;
+    if (g.windows > 0) return CRF_OK;
     const int windows = int((c->alloc_voxels + kWindowVoxels - 1) / kWindowVoxels);
-    const bool sec = !c->sec_members.empty();
+    const bool sec = !g.secondary.ptrs.empty();
     std::vector<const float*> table(size_t(windows) * size_t(c->cs) * (sec ? 2 : 1));
     for (int w = 0; w < windows; w++)
         for (int m = 0; m < c->cs; m++) {
-            table[(size_t(w) * (sec ? 2 : 1)) * size_t(c->cs) + size_t(m)] = c->members[size_t(m)] + size_t(w) * kWindowVoxels;
-            if (sec) table[(size_t(w) * 2 + 1) * size_t(c->cs) + size_t(m)] = c->sec_members[size_t(m)] + size_t(w) * kWindowVoxels;
+            table[(size_t(w) * (sec ? 2 : 1)) * size_t(c->cs) + size_t(m)] = g.members.f32(m) + size_t(w) * kWindowVoxels;
+            if (sec) table[(size_t(w) * 2 + 1) * size_t(c->cs) + size_t(m)] = g.secondary.f32(m) + size_t(w) * kWindowVoxels;
         }
-    if (c->d_window_tables) (void)hipFree(c->d_window_tables);
-    c->d_window_tables = nullptr;
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_window_tables), table.size() * sizeof(float*)));
-    CRF_HIP(c, hipMemcpy(c->d_window_tables, table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
-    c->windows = windows;
-    c->window_has_secondary = sec;
+    CRF_HIP(c, g.window_tables.reserve(table.size()));
+    CRF_HIP(c, hipMemcpy(g.window_tables.get(), table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
+    g.windows = windows;
+    g.window_has_secondary = sec;
     return CRF_OK;
 }
 
@@ -481,38 +491,27 @@ int ensure_windows(crf_context* c) {
 // duration of a launch; restores it on every exit path
 struct NarrowScope {
     crf_context* c;
-    const float** table;
-    const float** sec_table;
-    const void** format_table;
-    size_t voxels;
-    int vpt;
-    explicit NarrowScope(crf_context* ctx)
-        : c(ctx), table(ctx->d_member_table), sec_table(ctx->d_sec_table), format_table(ctx->d_narrow_table),
-          voxels(ctx->num_voxels), vpt(ctx->max_vpt) {}
+    const crf_launch_view whole;
+    explicit NarrowScope(crf_context* ctx) : c(ctx), whole(ctx->view) {}
     size_t select_window(int w) {  // returns the window's first voxel
-        const size_t per = size_t(c->window_has_secondary ? 2 : 1) * size_t(c->cs);
-        c->d_member_table = c->d_window_tables + size_t(w) * per;
-        if (c->window_has_secondary) c->d_sec_table = c->d_window_tables + size_t(w) * per + size_t(c->cs);
-        c->num_voxels = std::min(kWindowVoxels, c->alloc_voxels - size_t(w) * kWindowVoxels);
+        const crf_grid_state& g = c->grid;
+        const size_t per = size_t(g.window_has_secondary ? 2 : 1) * size_t(c->cs);
+        c->view.members = g.window_tables.get() + size_t(w) * per;
+        if (g.window_has_secondary) c->view.secondary = g.window_tables.get() + size_t(w) * per + size_t(c->cs);
+        c->view.num_voxels = std::min(kWindowVoxels, c->alloc_voxels - size_t(w) * kWindowVoxels);
         return size_t(w) * kWindowVoxels;
     }
     void select_range(int j, int scratch_set) {  // range j of ensure_host_ranges, writing the scratch of its stream
-        const float** range_table = c->d_chunk_tables + size_t(j) * size_t(c->cs);
-        if (c->chunk_native)
-            c->d_narrow_table = reinterpret_cast<const void**>(range_table);
+        const crf_grid_state& g = c->grid;
+        const void* const* range_table = g.chunk_tables.get() + size_t(j) * size_t(c->cs);
+        if (g.chunk_native)
+            c->view.narrow = range_table;
         else
-            c->d_member_table = range_table;
-        c->num_voxels = c->chunk_first[j + 1] - c->chunk_first[j];
-        c->scratch_set = scratch_set;
+            c->view.members = reinterpret_cast<const float* const*>(range_table);
+        c->view.num_voxels = g.chunk_first[j + 1] - g.chunk_first[j];
+        c->view.scratch_set = scratch_set;
     }
-    ~NarrowScope() {
-        c->scratch_set = 0;
-        c->d_member_table = table;
-        c->d_sec_table = sec_table;
-        c->d_narrow_table = format_table;
-        c->num_voxels = voxels;
-        c->max_vpt = vpt;
-    }
+    ~NarrowScope() { c->view = whole; }
 };
 
 // runs launch(out + first voxel of the window) for every window of a >= 4 GiB grid, or once for an ordinary grid
@@ -521,7 +520,7 @@ int for_each_window(crf_context* c, float* out, Launch&& launch) {
     if (!c->windowed) return launch(out);
     if (int r = ensure_windows(c)) return r;
     NarrowScope scope(c);
-    for (int w = 0; w < c->windows; w++) {
+    for (int w = 0; w < c->grid.windows; w++) {
         const size_t first = scope.select_window(w);
         if (int r = launch(out + first)) return r;
     }
@@ -535,33 +534,33 @@ int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream
     const char*& kernel = launch.info.kernel_name;
     hipError_t e = hipErrorNotSupported;
     if (p->measure == CRF_PEARSON) {
-        e = crf::launch_pearson_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, out, s);
+        e = crf::launch_pearson_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, out, s);
         kernel = "pearson_symmetric_kernel";
     } else if (p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) {
-        e = crf::launch_mi_kraskov_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->k,
-                                             kraskov_c_term(p->k, 1), p->measure == CRF_KMI_CC, c->d_tables, out, s);
+        e = crf::launch_mi_kraskov_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, p->k,
+                                             kraskov_c_term(p->k, 1), p->measure == CRF_KMI_CC, c->grid.tables.get(), out, s);
         kernel = "kraskov_direct_kernel";
     } else {  // Spearman, Kendall, the binned measures: sort-based where it applies, else the any-member-count kernel
         const char* force_direct = getenv("CRF_SYMMETRIC_DIRECT");  // tuning / tests: the any-member-count kernel
         if (!(force_direct && *force_direct == '1')) {
-            e = crf::launch_sorted_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->measure,
-                                             p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables,
+            e = crf::launch_sorted_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, p->measure,
+                                             p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, c->grid.tables.get(),
                                              out, s);
             kernel = "sorted_symmetric_kernel";
         }
         if (e == hipErrorNotSupported) {
-            if (int r = ensure_workspace(c, crf::direct_symmetric_workspace_bytes(c->cs, c->num_voxels, p->measure))) return r;
-            e = crf::launch_direct_symmetric(c->d_member_table, c->d_sec_table, c->cs, c->num_voxels, p->measure, p->num_bins,
-                                             p->min_ref, p->max_ref, p->min_query, p->max_query, c->d_tables,
-                                             c->scratch[0].workspace, out, s);
+            if (int r = ensure_workspace(c, crf::direct_symmetric_workspace_bytes(c->cs, c->view.num_voxels, p->measure))) return r;
+            e = crf::launch_direct_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, p->measure, p->num_bins,
+                                             p->min_ref, p->max_ref, p->min_query, p->max_query, c->grid.tables.get(),
+                                             c->grid.scratch[0].workspace.get(), out, s);
             kernel = "direct_symmetric_kernel";
         }
     }
     if (e == hipErrorNotSupported) {
-        if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, c->num_voxels))) return r;
+        if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, c->view.num_voxels))) return r;
         const crf::PairArgs a{p->measure, p->num_bins, p->k, 0, kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
-        e = crf::launch_pair_requests(c->d_member_table, c->d_sec_table, c->cs, c->xs, c->ys, c->num_voxels, nullptr,
-                                      c->num_voxels, a, c->d_tables, c->scratch[0].workspace, out, s);
+        e = crf::launch_pair_requests(c->view.members, c->view.secondary, c->cs, c->xs, c->ys, c->view.num_voxels, nullptr,
+                                      c->view.num_voxels, a, c->grid.tables.get(), c->grid.scratch[0].workspace.get(), out, s);
         kernel = "pair_request_kernel";
     }
     if (launch.e0 && launch.e1) (void)hipEventRecord(launch.e1, s);
@@ -633,7 +632,7 @@ int ensure_copy_pool(crf_context* c) {
     // one-off calibration: how many of the pool's threads move pinned -> pageable memory fastest on this host
     const size_t bytes = std::min<size_t>(c->alloc_voxels * sizeof(float), size_t(16) << 20);
     std::vector<char> dst(bytes, 1);
-    const char* src = reinterpret_cast<const char*>(c->h_staging);
+    const char* src = reinterpret_cast<const char*>(c->grid.staging.host());
     double best = 1e30;
     for (int t : {2, 4, 8, 12, 16}) {
         if (t > cap) break;
@@ -680,22 +679,21 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
     hipStream_t s = stream_of(c, stream);
     float* out = static_cast<float*>(device_out);
     const bool native = native_field(c, p);
-    if (ov && c->format != CRF_MEMBER_F32)
+    if (ov && c->grid.format != CRF_MEMBER_F32)
         return fail(c, CRF_ERR_UNSUPPORTED, "a direct reference read needs fp32 members");
     if (!native)
         if (int r = ensure_wide(c, s)) return r;
-    if (phase & 2u) c->last_format = native ? c->format : CRF_MEMBER_F32;
+    if (phase & 2u) c->last_format = native ? c->grid.format : CRF_MEMBER_F32;
     if (symmetric) {
         if (phase != 3u) return fail(c, CRF_ERR_ARGUMENT, "the symmetric mode has no reference-side preparation");
-        if (c->sec_members.empty())
+        if (c->grid.secondary.ptrs.empty())
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_SYMMETRIC needs secondary members (crf_upload_secondary_members)");
         return for_each_window(c, out, [&](float* o) { return compute_symmetric(c, p, o, s); });
     }
-    float* prep = c->d_prep;
+    float* prep = c->prep.get();
     if (slot >= 0) {
-        if (!c->d_prep_slots)
-            CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_prep_slots), size_t(CRF_PREPARED_SLOTS) * crf::kPrepBytes));
-        prep = c->d_prep_slots + size_t(slot) * (crf::kPrepBytes / sizeof(float));
+        CRF_HIP(c, c->prep_slots.reserve(size_t(CRF_PREPARED_SLOTS) * (crf::kPrepBytes / sizeof(float))));
+        prep = c->prep_slots.get() + size_t(slot) * (crf::kPrepBytes / sizeof(float));
     }
 
     // 1. reference vector (CorrelationCalculator.cpp:802-818): a device array, a host array (copied stream-ordered),
@@ -709,18 +707,18 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
         ref.table = ov->table;
         ref.voxel = ov->voxel;
     } else if (!ref.values && (p->flags & CRF_FLAG_REFERENCE_FROM_SECONDARY)) {
-        if (c->sec_members.empty())
+        if (c->grid.secondary.ptrs.empty())
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_REFERENCE_FROM_SECONDARY needs secondary members");
         size_t voxel;
         if (int r = ref_voxel(c, p->ref_x, p->ref_y, p->ref_z, &voxel)) return r;
-        CRF_HIP(c, crf::launch_gather_reference(c->d_sec_table, c->cs, voxel, c->d_ref, s));
-        ref.values = c->d_ref;
+        CRF_HIP(c, crf::launch_gather_reference(c->view.secondary, c->cs, voxel, c->grid.ref.get(), s));
+        ref.values = c->grid.ref.get();
     }
     if ((phase & 1u) && !ref.values && !ref.table) {
         if (p->reference_values) {
-            CRF_HIP(c, hipMemcpyAsync(c->d_ref, p->reference_values, sizeof(float) * size_t(c->cs),
+            CRF_HIP(c, hipMemcpyAsync(c->grid.ref.get(), p->reference_values, sizeof(float) * size_t(c->cs),
                                       hipMemcpyHostToDevice, s));
-            ref.values = c->d_ref;
+            ref.values = c->grid.ref.get();
         } else {
             if (int r = ref_voxel(c, p->ref_x, p->ref_y, p->ref_z, &ref.voxel)) return r;
         }
@@ -735,16 +733,16 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
     const int est = p->kraskov_estimator_index == 2 ? 2 : 1;  // clamp as CorrelationCalculator.cpp:765
     const crf::BinnedArgs ba{p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query,
                              p->measure == CRF_BINNED_MI_CC};
-    const crf_scratch& scratch = c->scratch[c->scratch_set];  // filled in by ensure_todo / ensure_workspace below
+    const crf_scratch& scratch = c->grid.scratch[c->view.scratch_set];  // filled in by ensure_todo / ensure_workspace below
     hipError_t e = hipErrorNotSupported;
     if (p->measure != CRF_PEARSON && c->cs > crf::kMaxSortMembers) {
         // any-member-count path: a specialised kernel where one applies, else kernels_generic.hip
         if (binned) {  // O(cs) histogram kernel, unless there are too many bins for the LDS rows
-            e = crf::launch_mi_binned_hist(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s, e0,
+            e = crf::launch_mi_binned_hist(c->view.members, c->cs, c->view.num_voxels, ref, ba, c->grid.tables.get(), prep, out, s, e0,
                                            e1, info);
         } else if (kraskov) {  // tile-free single-sweep top-K kernel, unless k > 128 or the tables are beyond LDS
             const crf::KraskovArgs ka{p->k, est, p->measure == CRF_KMI_CC, kraskov_c_term(p->k, est)};
-            e = crf::launch_mi_kraskov_direct(c->d_member_table, c->cs, c->num_voxels, ref, ka, c->d_tables, prep, out, s,
+            e = crf::launch_mi_kraskov_direct(c->view.members, c->cs, c->view.num_voxels, ref, ka, c->grid.tables.get(), prep, out, s,
                                               e0, e1, info);
         }
         if (e == hipErrorNotSupported) {  // the O(cs^2) counting / repeated-minimum kernels
@@ -754,20 +752,20 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
             const bool rank_measure = p->measure == CRF_SPEARMAN || p->measure == CRF_KENDALL;
             if (rank_measure && c->cs <= 256)
                 if (int r = ensure_todo(c)) return r;
-            e = crf::launch_generic(c->d_member_table, c->cs, c->num_voxels, ref, ga, c->d_tables, prep, scratch.workspace,
-                                    out, s, e0, e1, info, rank_measure ? scratch.todo : nullptr);
+            e = crf::launch_generic(c->view.members, c->cs, c->view.num_voxels, ref, ga, c->grid.tables.get(), prep, scratch.workspace.get(),
+                                    out, s, e0, e1, info, rank_measure ? scratch.todo.get() : nullptr);
         }
         return launch.finish(e);
+    }
+    if (native && (phase & 1u) && !ref.values) {  // the reference point: its converted values (fp32), through grid.ref
+        CRF_HIP(c, crf::launch_gather_reference_narrow(c->view.narrow, c->grid.format, c->cs, ref.voxel, c->grid.ref.get(), s));
+        ref.values = c->grid.ref.get();
     }
     switch (p->measure) {
         case CRF_PEARSON: {
             if (native) {
-                if ((phase & 1u) && !ref.values) {  // the reference point: its converted values, through d_ref
-                    CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, ref.voxel, c->d_ref, s));
-                    ref.values = c->d_ref;
-                }
-                const uintptr_t vector_bytes = c->format == CRF_MEMBER_U8 ? 16 : 8;  // one lane's results
-                e = crf::launch_pearson_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels,
+                const uintptr_t vector_bytes = c->grid.format == CRF_MEMBER_U8 ? 16 : 8;  // one lane's results
+                e = crf::launch_pearson_narrow(c->view.narrow, c->grid.format, c->cs, c->view.num_voxels,
                                                reinterpret_cast<uintptr_t>(out) % vector_bytes == 0, ref, prep, out, s, e0,
                                                e1, info);
                 if (phase & 2u) c->last_layout = CRF_MEMBER_LAYOUT_RAW;
@@ -776,7 +774,7 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
             crf::PackedMembers packed;
             if (phase & 2u)
                 if (int r = ensure_packed(c, s, &packed)) return r;
-            e = crf::launch_pearson(c->d_member_table, c->cs, c->num_voxels, std::min(c->max_vpt, alignment_vpt(out)), ref,
+            e = crf::launch_pearson(c->view.members, c->cs, c->view.num_voxels, std::min(c->view.max_vpt, alignment_vpt(out)), ref,
                                     prep, out, s, e0, e1, info, packed);
             if (phase & 2u) c->last_layout = packed.header ? CRF_MEMBER_LAYOUT_PACKED : CRF_MEMBER_LAYOUT_RAW;
             break;
@@ -784,41 +782,33 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
         case CRF_SPEARMAN:
         case CRF_KENDALL:
             if (native) {  // on narrow members: one pass, no todo list; the reference side is fp32 as ever
-                if ((phase & 1u) && !ref.values) {
-                    CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, ref.voxel, c->d_ref, s));
-                    ref.values = c->d_ref;
-                }
                 e = (p->measure == CRF_SPEARMAN ? crf::launch_spearman_narrow : crf::launch_kendall_narrow)(
-                    c->d_narrow_table, c->format, c->cs, c->num_voxels, ref, prep, out, s, e0, e1, info);
+                    c->view.narrow, c->grid.format, c->cs, c->view.num_voxels, ref, prep, out, s, e0, e1, info);
                 break;
             }
             if (c->cs > 16)
                 if (int r = ensure_todo(c)) return r;
             e = (p->measure == CRF_SPEARMAN ? crf::launch_spearman : crf::launch_kendall)(
-                c->d_member_table, c->cs, c->num_voxels, ref, prep, scratch.todo, out, s, e0, e1, info);
+                c->view.members, c->cs, c->view.num_voxels, ref, prep, scratch.todo.get(), out, s, e0, e1, info);
             break;
         case CRF_MI_BINNED:
         case CRF_BINNED_MI_CC:
             if (native) {  // binned MI on narrow members: the reference side is fp32 as ever
-                if ((phase & 1u) && !ref.values) {
-                    CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, ref.voxel, c->d_ref, s));
-                    ref.values = c->d_ref;
-                }
-                e = crf::launch_mi_binned_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, ref, ba, c->d_tables,
+                e = crf::launch_mi_binned_narrow(c->view.narrow, c->grid.format, c->cs, c->view.num_voxels, ref, ba, c->grid.tables.get(),
                                                  prep, out, s, e0, e1, info);
                 break;
             }
             if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1')  // tuning: histogram kernel for any cs
-                e = crf::launch_mi_binned_hist(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s,
+                e = crf::launch_mi_binned_hist(c->view.members, c->cs, c->view.num_voxels, ref, ba, c->grid.tables.get(), prep, out, s,
                                                e0, e1, info);
             if (e == hipErrorNotSupported)
-                e = crf::launch_mi_binned(c->d_member_table, c->cs, c->num_voxels, ref, ba, c->d_tables, prep, out, s,
+                e = crf::launch_mi_binned(c->view.members, c->cs, c->view.num_voxels, ref, ba, c->grid.tables.get(), prep, out, s,
                                           e0, e1, info);
             break;
         case CRF_MI_KRASKOV:
         case CRF_KMI_CC: {
             const crf::KraskovArgs ka{p->k, est, p->measure == CRF_KMI_CC, kraskov_c_term(p->k, est)};
-            e = crf::launch_mi_kraskov(c->d_member_table, c->cs, c->num_voxels, ref, ka, c->d_tables, prep, out, s,
+            e = crf::launch_mi_kraskov(c->view.members, c->cs, c->view.num_voxels, ref, ka, c->grid.tables.get(), prep, out, s,
                                        e0, e1, info);
             break;
         }
@@ -848,7 +838,7 @@ int compute_impl(crf_context* c, const crf_params* p, const void* device_referen
 // CRF_FLAG_ABSOLUTE_VALUE after a device evaluation (opt-in: what the reference's accelerator paths do)
 int apply_abs(crf_context* c, const crf_params* p, void* device_out, void* stream) {
     if (p->flags & CRF_FLAG_ABSOLUTE_VALUE)
-        CRF_HIP(c, crf::launch_abs(static_cast<float*>(device_out), c->num_voxels, stream_of(c, stream)));
+        CRF_HIP(c, crf::launch_abs(static_cast<float*>(device_out), c->view.num_voxels, stream_of(c, stream)));
     return CRF_OK;
 }
 
@@ -856,12 +846,13 @@ int apply_abs(crf_context* c, const crf_params* p, void* device_out, void* strea
 // first voxel), so that every per-voxel kernel can be launched on a range without knowing about ranges.  Range lengths
 // are multiples of 1024 voxels (4 KiB: every range stays as aligned as the members themselves) and shrink towards the
 // end: the copy of the last range into the caller's buffer is the only host work no kernel hides.
-// native: the tables hold the narrow members' pointers (the native Pearson, Kendall, Spearman and binned-MI fields), advanced
-// by whole elements; a range starts at a multiple of 1024 voxels, so they stay as aligned as the members (4 bytes for
-// Pearson, the element for the others) and every range but the last is whole dwords.
+// native (the evaluation is a native_field one): the tables point into the narrow members, advanced by whole elements.
+// A range starts at a multiple of 1024 voxels, so its pointers are as aligned as the members' own (the fact native_field
+// asked about) and every range but the last is whole dwords.  Else they point into the fp32 members.
 int ensure_host_ranges(crf_context* c, bool native) {
-    if (c->host_chunks > 0 && c->chunk_native == native) return CRF_OK;
-    c->host_chunks = 0;
+    crf_grid_state& g = c->grid;
+    if (g.host_chunks > 0 && g.chunk_native == native) return CRF_OK;
+    g.host_chunks = 0;
     const size_t n = c->alloc_voxels;
     std::vector<size_t> first{0};
     const int forced = env_int_or("CRF_HOST_CHUNKS", 0);
@@ -898,26 +889,22 @@ int ensure_host_ranges(crf_context* c, bool native) {
     }
     const int ranges = int(first.size());
     first.push_back(n);
-    std::vector<const float*> table(size_t(ranges) * size_t(c->cs));
-    const size_t element = crf::member_format_bytes(c->format);
+    std::vector<const void*> table(size_t(ranges) * size_t(c->cs));
+    const crf_member_set& set = native ? g.narrow : g.members;
+    const size_t element = crf::member_format_bytes(set.format);
     for (int j = 0; j < ranges; j++)
         for (int m = 0; m < c->cs; m++)
             table[size_t(j) * size_t(c->cs) + size_t(m)] =
-                native ? reinterpret_cast<const float*>(static_cast<const char*>(c->narrow[size_t(m)]) + first[size_t(j)] * element)
-                       : c->members[size_t(m)] + first[size_t(j)];
-    if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
-    c->d_chunk_tables = nullptr;
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_chunk_tables), table.size() * sizeof(float*)));
-    CRF_HIP(c, hipMemcpy(c->d_chunk_tables, table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
-    if (!c->copy_stream) CRF_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int j = 0; j < ranges; j++)
-        if (!c->chunk_done[j]) CRF_HIP(c, hipEventCreateWithFlags(&c->chunk_done[j], hipEventDisableTiming));
-    for (int j = 0; j < ranges; j++)
-        if (!c->chunk_copied[j]) CRF_HIP(c, hipEventCreateWithFlags(&c->chunk_copied[j], hipEventDisableTiming));
-    if (!c->prep_done) CRF_HIP(c, hipEventCreateWithFlags(&c->prep_done, hipEventDisableTiming));
-    for (int j = 0; j <= ranges; j++) c->chunk_first[j] = first[size_t(j)];
-    c->host_chunks = ranges;
-    c->chunk_native = native;
+                static_cast<const char*>(set.ptrs[size_t(m)]) + first[size_t(j)] * element;
+    CRF_HIP(c, g.chunk_tables.reserve(table.size()));
+    CRF_HIP(c, hipMemcpy(g.chunk_tables.get(), table.data(), table.size() * sizeof(void*), hipMemcpyHostToDevice));
+    CRF_HIP(c, c->copy_stream.create());
+    for (int j = 0; j < ranges; j++) CRF_HIP(c, c->chunk_done[j].create(hipEventDisableTiming));
+    for (int j = 0; j < ranges; j++) CRF_HIP(c, c->chunk_copied[j].create(hipEventDisableTiming));
+    CRF_HIP(c, c->prep_done.create(hipEventDisableTiming));
+    for (int j = 0; j <= ranges; j++) g.chunk_first[j] = first[size_t(j)];
+    g.host_chunks = ranges;
+    g.chunk_native = native;
     return CRF_OK;
 }
 
@@ -947,8 +934,8 @@ int to_host(crf_context* c, float* host_out, DeviceCall&& device_call) {
     if (!host_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
     if (int r = bind_device(c)) return r;
     if (int r = ensure_out(c)) return r;
-    if (int r = device_call(c->d_out)) return r;
-    return copy_result_to_host(c, c->d_out, host_out, c->alloc_voxels);
+    if (int r = device_call(c->grid.out.get())) return r;
+    return copy_result_to_host(c, c->grid.out.get(), host_out, c->alloc_voxels);
 }
 
 }  // namespace
@@ -992,49 +979,18 @@ int crf_create(int device_ordinal, crf_context** out_ctx) {
         return CRF_ERR_DEVICE;
     };
     if ((e = hipSetDevice(device_ordinal)) != hipSuccess) return bail("hipSetDevice", e);
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
-        return bail("hipStreamCreate", e);
-    if ((e = hipMalloc(&c->d_prep, crf::kPrepBytes)) != hipSuccess) return bail("hipMalloc(prep)", e);
-    if ((e = hipMalloc(&c->d_minmax, 2 * sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc(minmax)", e);
+    if ((e = c->stream.create()) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = c->prep.reserve(crf::kPrepBytes / sizeof(float))) != hipSuccess) return bail("hipMalloc(prep)", e);
+    if ((e = c->minmax.reserve(2)) != hipSuccess) return bail("hipMalloc(minmax)", e);
     *out_ctx = c;
     return CRF_OK;
 }
 
+// The owners in the context release everything, in the order crf_context.h states.
 void crf_destroy(crf_context* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    release_members(c);
-    release_secondary(c);
-    if (c->d_member_table) (void)hipFree(c->d_member_table);
-    if (c->d_narrow_table) (void)hipFree(c->d_narrow_table);
-    if (c->d_sec_table) (void)hipFree(c->d_sec_table);
-    if (c->d_ref) (void)hipFree(c->d_ref);
-    if (c->d_prep) (void)hipFree(c->d_prep);
-    if (c->d_prep_slots) (void)hipFree(c->d_prep_slots);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_tables) (void)hipFree(c->d_tables);
-    free_scratch(c);
-    if (c->d_requests) (void)hipFree(c->d_requests);
-    if (c->d_request_out) (void)hipFree(c->d_request_out);
-    if (c->d_minmax) (void)hipFree(c->d_minmax);
-    if (c->d_pack_fallbacks) (void)hipFree(c->d_pack_fallbacks);
-    if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
-    c->copy_pool.reset();
-    if (c->h_staging) (void)hipHostFree(c->h_staging);
-    if (c->prep_done) (void)hipEventDestroy(c->prep_done);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    for (hipEvent_t e : c->chunk_done)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->chunk_copied)
-        if (e) (void)hipEventDestroy(e);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (auto& p : c->ev_pending) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
-    }
-    for (auto e : c->ev_free) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1045,53 +1001,31 @@ int crf_set_grid(crf_context* c, int xs, int ys, int zs, int cs) {
     const size_t n = size_t(xs) * size_t(ys) * size_t(zs);
     if (int r = bind_device(c)) return r;
     CRF_HIP(c, hipDeviceSynchronize());  // evaluations the caller left in flight on its own streams still read the scratch
-    release_members(c);
-    release_secondary(c);
-    if (c->d_member_table) (void)hipFree(c->d_member_table);
-    if (c->d_narrow_table) (void)hipFree(c->d_narrow_table);
-    c->d_narrow_table = nullptr;
-    if (c->d_sec_table) (void)hipFree(c->d_sec_table);
-    c->d_sec_table = nullptr;
-    if (c->d_ref) (void)hipFree(c->d_ref);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_tables) (void)hipFree(c->d_tables);
-    free_scratch(c);
-    if (c->d_chunk_tables) (void)hipFree(c->d_chunk_tables);
-    if (c->h_staging) (void)hipHostFree(c->h_staging);
-    c->h_staging = nullptr;
-    c->d_staging = nullptr;
-    c->d_chunk_tables = nullptr;
-    c->host_chunks = 0;
-    c->d_tables = nullptr;
-    c->d_member_table = nullptr;
-    c->d_ref = nullptr;
-    c->d_out = nullptr;
+    c->grid = crf_grid_state{};  // the members, everything derived from them and everything sized for the old grid
+    c->view = crf_launch_view{};
     c->xs = xs;
     c->ys = ys;
     c->zs = zs;
     c->cs = cs;
-    c->num_voxels = n;
     c->alloc_voxels = n;
     // The kernels address a member with 32-bit byte offsets, and their out-of-range sentinel offset (crf_device.h
     // kOutOfRangeOffset = 0xFFFFFFF0) must lie beyond the end of every member: a member volume of 4 GiB or more (1024^3 is
     // exactly 4 GiB; the reference has no limit) is evaluated in WINDOWS of kWindowVoxels voxels, one launch each, through
     // member-pointer tables advanced by the window's first voxel (ensure_windows below).
     c->windowed = n * sizeof(float) >= size_t(0xFFFFFFF0u);
-    if (c->d_window_tables) (void)hipFree(c->d_window_tables);
-    c->d_window_tables = nullptr;
-    c->windows = 0;
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_member_table), sizeof(float*) * size_t(cs)));
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_narrow_table), sizeof(void*) * size_t(cs)));
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_ref), sizeof(float) * size_t(cs)));
+    CRF_HIP(c, c->grid.members.table.reserve(size_t(cs)));
+    CRF_HIP(c, c->grid.narrow.table.reserve(size_t(cs)));
+    CRF_HIP(c, c->grid.ref.reserve(size_t(cs)));
     const std::vector<double> tables = build_tables(cs);
-    CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_tables), tables.size() * sizeof(double)));
-    CRF_HIP(c, hipMemcpy(c->d_tables, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice));
+    CRF_HIP(c, c->grid.tables.reserve(tables.size()));
+    CRF_HIP(c, hipMemcpy(c->grid.tables.get(), tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->view = whole_view(c);
     return CRF_OK;
 }
 
 int crf_set_kraskov_noise(crf_context* c, const double* ref_noise, const double* query_noise) {
     if (!c) return CRF_ERR_ARGUMENT;
-    if (c->cs <= 0 || !c->d_tables) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
+    if (c->cs <= 0 || !c->grid.tables) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
     if ((ref_noise == nullptr) != (query_noise == nullptr))
         return fail(c, CRF_ERR_ARGUMENT, "crf_set_kraskov_noise: give both tables, or NULL for both (default stream)");
     if (int r = bind_device(c)) return r;
@@ -1110,116 +1044,35 @@ int crf_set_kraskov_noise(crf_context* c, const double* ref_noise, const double*
         std::copy(t.begin() + 2 * (c->cs + 1), t.end(), both.begin());
     }
     CRF_HIP(c, hipStreamSynchronize(c->stream));
-    CRF_HIP(c, hipMemcpy(c->d_tables + 2 * (cs + 1), both.data(), both.size() * sizeof(double), hipMemcpyHostToDevice));
+    CRF_HIP(c, hipMemcpy(c->grid.tables.get() + 2 * (cs + 1), both.data(), both.size() * sizeof(double), hipMemcpyHostToDevice));
     return CRF_OK;
 }
 
 int crf_upload_members(crf_context* c, const float* const* host_members) {
-    if (!c || !host_members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
-    for (int i = 0; i < c->cs; i++)
-        if (!host_members[i]) return fail(c, CRF_ERR_ARGUMENT, fmt("member %d is a null pointer", i));
-    if (int r = bind_device(c)) return r;
-    release_members(c);
-    // Member stride: volume size rounded up to 256 B so every member starts 256-B aligned (wide vector loads).
-    const size_t stride = (c->num_voxels + 63) & ~size_t(63);
-    c->owned_stride = stride;
-    CRF_HIP(c, hipMalloc(&c->owned_block, stride * sizeof(float) * size_t(c->cs)));
-    c->members.resize(size_t(c->cs));
-    for (int i = 0; i < c->cs; i++) {
-        float* dst = static_cast<float*>(c->owned_block) + stride * size_t(i);
-        c->members[size_t(i)] = dst;
-        CRF_HIP(c, hipMemcpyAsync(dst, host_members[i], c->num_voxels * sizeof(float), hipMemcpyHostToDevice,
-                                  c->stream));
-    }
-    return install_member_table(c);
+    return set_members(c, false, CRF_MEMBER_F32, reinterpret_cast<const void* const*>(host_members), true, "member");
 }
 
 int crf_bind_members_device(crf_context* c, const void* const* device_members) {
-    if (!c || !device_members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
-    for (int i = 0; i < c->cs; i++)
-        if (!device_members[i]) return fail(c, CRF_ERR_ARGUMENT, fmt("member %d is a null pointer", i));
-    if (int r = bind_device(c)) return r;
-    release_members(c);
-    c->members.resize(size_t(c->cs));
-    for (int i = 0; i < c->cs; i++) c->members[size_t(i)] = static_cast<const float*>(device_members[i]);
-    return install_member_table(c);
-}
-
-// the checks the two format calls share; *narrow: a narrow format (else the call is the fp32 call)
-static int check_member_format(crf_context* c, int format, const void* const* members, bool* narrow) {
-    if (!c || !members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (format < CRF_MEMBER_F32 || format > CRF_MEMBER_F16)
-        return fail(c, CRF_ERR_ARGUMENT, fmt("unknown member format %d", format));
-    *narrow = format != CRF_MEMBER_F32;
-    if (!*narrow) return CRF_OK;
-    if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
-    for (int i = 0; i < c->cs; i++)
-        if (!members[i]) return fail(c, CRF_ERR_ARGUMENT, fmt("member %d is a null pointer", i));
-    // the native kernel addresses a member with 32-bit byte offsets (crf_internal.h: kNarrowMaxBytes, just under 4 GiB)
-    if (c->alloc_voxels * crf::member_format_bytes(format) >= crf::kNarrowMaxBytes)
-        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%s members of 4 GiB or more are not supported (%zu voxels per member)",
-                                                format_name(format), c->alloc_voxels));
-    return bind_device(c);
+    return set_members(c, false, CRF_MEMBER_F32, device_members, false, "member");
 }
 
 int crf_upload_members_format(crf_context* c, int format, const void* const* host_members) {
-    bool narrow = false;
-    if (int r = check_member_format(c, format, host_members, &narrow)) return r;
-    if (!narrow) return crf_upload_members(c, reinterpret_cast<const float* const*>(host_members));
-    release_members(c);
-    const size_t bytes = c->num_voxels * crf::member_format_bytes(format);
-    const size_t stride = (bytes + 255) & ~size_t(255);  // every member starts 256-B aligned
-    CRF_HIP(c, hipMalloc(&c->narrow_owned_block, stride * size_t(c->cs)));
-    c->format = format;
-    c->narrow.resize(size_t(c->cs));
-    for (int i = 0; i < c->cs; i++) {
-        char* dst = static_cast<char*>(c->narrow_owned_block) + stride * size_t(i);
-        c->narrow[size_t(i)] = dst;
-        CRF_HIP(c, hipMemcpyAsync(dst, host_members[i], bytes, hipMemcpyHostToDevice, c->stream));
-    }
-    return install_narrow_table(c);
+    return set_members(c, false, format, host_members, true, "member");
 }
 
 int crf_bind_members_device_format(crf_context* c, int format, const void* const* device_members) {
-    bool narrow = false;
-    if (int r = check_member_format(c, format, device_members, &narrow)) return r;
-    if (!narrow) return crf_bind_members_device(c, device_members);
-    release_members(c);
-    c->format = format;
-    c->narrow.assign(device_members, device_members + c->cs);
-    return install_narrow_table(c);
+    return set_members(c, false, format, device_members, false, "member");
 }
 
-int crf_member_format(const crf_context* c) { return c ? c->format : CRF_MEMBER_F32; }
+int crf_member_format(const crf_context* c) { return c ? c->grid.format : CRF_MEMBER_F32; }
 
 int crf_last_member_format(const crf_context* c) { return c ? c->last_format : CRF_MEMBER_F32; }
 
-size_t crf_wide_copy_bytes(const crf_context* c) {
-    if (!c || !c->wide_block) return 0;
-    return ((c->alloc_voxels + 63) & ~size_t(63)) * sizeof(float) * size_t(c->cs);  // ensure_wide's block
-}
+size_t crf_wide_copy_bytes(const crf_context* c) { return c ? c->grid.wide.count() * sizeof(float) : 0; }
 
 int crf_member_minmax(crf_context* c, float* out_min, float* out_max) {
     if (int r = check_ready(c)) return r;
-    if (!out_min || !out_max) return fail(c, CRF_ERR_ARGUMENT, "null output");
-    if (!c->minmax_valid) {
-        if (int r = bind_device(c)) return r;
-        if (c->format != CRF_MEMBER_F32)  // the narrow members as stored: no fp32 copy
-            CRF_HIP(c, crf::launch_minmax_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, c->d_minmax, c->stream));
-        else
-            CRF_HIP(c, crf::launch_minmax(c->d_member_table, c->cs, c->num_voxels, c->d_minmax, c->stream));
-        uint32_t keys[2];
-        CRF_HIP(c, hipMemcpyAsync(keys, c->d_minmax, sizeof keys, hipMemcpyDeviceToHost, c->stream));
-        CRF_HIP(c, hipStreamSynchronize(c->stream));
-        c->min_v = crf::minmax_key_to_float(keys[0]);
-        c->max_v = crf::minmax_key_to_float(keys[1]);
-        c->minmax_valid = true;
-    }
-    *out_min = c->min_v;
-    *out_max = c->max_v;
-    return CRF_OK;
+    return member_minmax(c, c->grid.format == CRF_MEMBER_F32 ? c->grid.members : c->grid.narrow, out_min, out_max);
 }
 
 int crf_member_minmax_divergent(crf_context* c, int secondary, float* out_min, float* out_max) {
@@ -1232,53 +1085,19 @@ int crf_member_minmax_divergent(crf_context* c, int secondary, float* out_min, f
 }
 
 int crf_upload_secondary_members(crf_context* c, const float* const* host_members) {
-    if (!c || !host_members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
-    for (int i = 0; i < c->cs; i++)
-        if (!host_members[i]) return fail(c, CRF_ERR_ARGUMENT, fmt("secondary member %d is a null pointer", i));
-    if (int r = bind_device(c)) return r;
-    release_secondary(c);
-    const size_t stride = (c->num_voxels + 63) & ~size_t(63);
-    CRF_HIP(c, hipMalloc(&c->sec_owned_block, stride * sizeof(float) * size_t(c->cs)));
-    c->sec_members.resize(size_t(c->cs));
-    for (int i = 0; i < c->cs; i++) {
-        float* dst = static_cast<float*>(c->sec_owned_block) + stride * size_t(i);
-        c->sec_members[size_t(i)] = dst;
-        CRF_HIP(c, hipMemcpyAsync(dst, host_members[i], c->num_voxels * sizeof(float), hipMemcpyHostToDevice,
-                                  c->stream));
-    }
-    return install_secondary_table(c);
+    return set_members(c, true, CRF_MEMBER_F32, reinterpret_cast<const void* const*>(host_members), true,
+                       "secondary member");
 }
 
 int crf_bind_secondary_members_device(crf_context* c, const void* const* device_members) {
-    if (!c || !device_members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
-    if (c->cs <= 0) return fail(c, CRF_ERR_STATE, "crf_set_grid has not been called");
-    for (int i = 0; i < c->cs; i++)
-        if (!device_members[i]) return fail(c, CRF_ERR_ARGUMENT, fmt("secondary member %d is a null pointer", i));
-    if (int r = bind_device(c)) return r;
-    release_secondary(c);
-    c->sec_members.resize(size_t(c->cs));
-    for (int i = 0; i < c->cs; i++) c->sec_members[size_t(i)] = static_cast<const float*>(device_members[i]);
-    return install_secondary_table(c);
+    return set_members(c, true, CRF_MEMBER_F32, device_members, false, "secondary member");
 }
 
 int crf_secondary_member_minmax(crf_context* c, float* out_min, float* out_max) {
     if (int r = check_ready(c)) return r;
     if (!out_min || !out_max) return fail(c, CRF_ERR_ARGUMENT, "null output");
-    if (c->sec_members.empty()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
-    if (!c->sec_minmax_valid) {
-        if (int r = bind_device(c)) return r;
-        CRF_HIP(c, crf::launch_minmax(c->d_sec_table, c->cs, c->num_voxels, c->d_minmax, c->stream));
-        uint32_t keys[2];
-        CRF_HIP(c, hipMemcpyAsync(keys, c->d_minmax, sizeof keys, hipMemcpyDeviceToHost, c->stream));
-        CRF_HIP(c, hipStreamSynchronize(c->stream));
-        c->sec_min_v = crf::minmax_key_to_float(keys[0]);
-        c->sec_max_v = crf::minmax_key_to_float(keys[1]);
-        c->sec_minmax_valid = true;
-    }
-    *out_min = c->sec_min_v;
-    *out_max = c->sec_max_v;
-    return CRF_OK;
+    if (c->grid.secondary.ptrs.empty()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
+    return member_minmax(c, c->grid.secondary, out_min, out_max);
 }
 
 int crf_gather_reference_device(crf_context* c, int x, int y, int z, void* device_out, void* stream) {
@@ -1288,11 +1107,11 @@ int crf_gather_reference_device(crf_context* c, int x, int y, int z, void* devic
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
-    if (c->format != CRF_MEMBER_F32)  // the converted values of the narrow members: no fp32 copy
-        CRF_HIP(c, crf::launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, voxel,
+    if (c->grid.format != CRF_MEMBER_F32)  // the converted values of the narrow members: no fp32 copy
+        CRF_HIP(c, crf::launch_gather_reference_narrow(c->view.narrow, c->grid.format, c->cs, voxel,
                                                        static_cast<float*>(device_out), s));
     else
-        CRF_HIP(c, crf::launch_gather_reference(c->d_member_table, c->cs, voxel, static_cast<float*>(device_out), s));
+        CRF_HIP(c, crf::launch_gather_reference(c->view.members, c->cs, voxel, static_cast<float*>(device_out), s));
     return CRF_OK;
 }
 
@@ -1309,19 +1128,19 @@ int crf_gather_reference_rows_device(crf_context* c, const int32_t* xyz, int num
     }
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
-    if (c->format != CRF_MEMBER_F32)
-        CRF_HIP(c, crf::launch_gather_reference_rows_narrow(c->d_narrow_table, c->format, c->cs, rows, num_rows,
+    if (c->grid.format != CRF_MEMBER_F32)
+        CRF_HIP(c, crf::launch_gather_reference_rows_narrow(c->view.narrow, c->grid.format, c->cs, rows, num_rows,
                                                             static_cast<float*>(device_rows), s));
     else
-        CRF_HIP(c, crf::launch_gather_reference_rows(c->d_member_table, c->cs, rows, num_rows,
+        CRF_HIP(c, crf::launch_gather_reference_rows(c->view.members, c->cs, rows, num_rows,
                                                      static_cast<float*>(device_rows), s));
     return CRF_OK;
 }
 
 int crf_gather_reference(crf_context* c, int x, int y, int z, float* host_out) {
     if (!host_out) return fail(c, CRF_ERR_ARGUMENT, "null output");
-    if (int r = crf_gather_reference_device(c, x, y, z, c ? c->d_ref : nullptr, nullptr)) return r;
-    CRF_HIP(c, hipMemcpyAsync(host_out, c->d_ref, sizeof(float) * size_t(c->cs), hipMemcpyDeviceToHost, c->stream));
+    if (int r = crf_gather_reference_device(c, x, y, z, c ? c->grid.ref.get() : nullptr, nullptr)) return r;
+    CRF_HIP(c, hipMemcpyAsync(host_out, c->grid.ref.get(), sizeof(float) * size_t(c->cs), hipMemcpyDeviceToHost, c->stream));
     CRF_HIP(c, hipStreamSynchronize(c->stream));
     return CRF_OK;
 }
@@ -1332,31 +1151,31 @@ namespace crf {
 
 int gather_reference_to(crf_context* c, bool secondary, int x, int y, int z, float* device_out, hipStream_t s) {
     if (int r = check_ready(c)) return r;
-    if (secondary && c->sec_members.empty()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
+    if (secondary && c->grid.secondary.ptrs.empty()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
     size_t voxel;
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
-    if (!secondary && c->format != CRF_MEMBER_F32)
-        CRF_HIP(c, launch_gather_reference_narrow(c->d_narrow_table, c->format, c->cs, voxel, device_out, s));
+    if (!secondary && c->grid.format != CRF_MEMBER_F32)
+        CRF_HIP(c, launch_gather_reference_narrow(c->view.narrow, c->grid.format, c->cs, voxel, device_out, s));
     else
-        CRF_HIP(c, launch_gather_reference(secondary ? c->d_sec_table : c->d_member_table, c->cs, voxel, device_out, s));
+        CRF_HIP(c, launch_gather_reference(secondary ? c->view.secondary : c->view.members, c->cs, voxel, device_out, s));
     return CRF_OK;
 }
 
 int second_stream(crf_context* c, hipStream_t* out) {
     if (int r = bind_device(c)) return r;
-    if (!c->stream2) CRF_HIP(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+    CRF_HIP(c, c->stream2.create());
     *out = c->stream2;
     return CRF_OK;
 }
 
 int reference_override(crf_context* owner, bool secondary, int x, int y, int z, RefOverride* out) {
     if (int r = check_ready(owner)) return r;
-    if (secondary && owner->sec_members.empty()) return fail(owner, CRF_ERR_STATE, "no secondary members are bound");
+    if (secondary && owner->grid.secondary.ptrs.empty()) return fail(owner, CRF_ERR_STATE, "no secondary members are bound");
     if (int r = ref_voxel(owner, x, y, z, &out->voxel)) return r;
-    if (!secondary && owner->format != CRF_MEMBER_F32)
+    if (!secondary && owner->grid.format != CRF_MEMBER_F32)
         return fail(owner, CRF_ERR_UNSUPPORTED, "a direct reference read needs fp32 members");
-    out->table = secondary ? owner->d_sec_table : owner->d_member_table;
+    out->table = secondary ? owner->view.secondary : owner->view.members;
     return CRF_OK;
 }
 
@@ -1387,21 +1206,16 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
                         !c->windowed && env_int_or("CRF_PLAIN_D2H", 0) != 1;
     if (!ranged) {
         if (int r = ensure_out(c)) return r;
-        if (int r = compute_device_ex(c, p, device_reference_values, c->d_out, nullptr, ov)) return r;
-        return copy_result_to_host(c, c->d_out, host_out, c->alloc_voxels);
+        if (int r = compute_device_ex(c, p, device_reference_values, c->grid.out.get(), nullptr, ov)) return r;
+        return copy_result_to_host(c, c->grid.out.get(), host_out, c->alloc_voxels);
     }
     const bool native = native_field(c, p);
     if (!native)
         if (int r = ensure_wide(c, c->stream)) return r;  // (the second stream is ordered behind the preparation below)
     if (int r = ensure_host_ranges(c, native)) return r;
-    const int ranges = c->host_chunks;
+    const int ranges = c->grid.host_chunks;
     // pinned, device-mapped staging for the whole local result
-    if (!c->h_staging) {
-        CRF_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_staging), bytes, hipHostMallocMapped));
-        void* dev = nullptr;
-        CRF_HIP(c, hipHostGetDevicePointer(&dev, c->h_staging, 0));
-        c->d_staging = static_cast<float*>(dev);
-    }
+    CRF_HIP(c, c->grid.staging.allocate(c->alloc_voxels));
     if (int r = ensure_copy_pool(c)) return r;
     const char* path_env = getenv("CRF_HOST_PATH");
     const bool dma = (path_env && strcmp(path_env, "dma") == 0) || (p->flags & CRF_FLAG_ABSOLUTE_VALUE);
@@ -1420,7 +1234,7 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
 
     // 0. host side first: the copier threads start faulting the destination in while the launches below are issued
     char* dst = reinterpret_cast<char*>(host_out);
-    const char* src = reinterpret_cast<const char*>(c->h_staging);
+    const char* src = reinterpret_cast<const char*>(c->grid.staging.host());
     if (huge && fault_mode != 0) {
         const uintptr_t a = (reinterpret_cast<uintptr_t>(dst) + (size_t(2) << 20) - 1) & ~((uintptr_t(2) << 20) - 1);
         const uintptr_t e = (reinterpret_cast<uintptr_t>(dst) + bytes) & ~((uintptr_t(2) << 20) - 1);
@@ -1429,7 +1243,7 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
     for (int j = 0; j < ranges; j++) c->chunk_ready[j].store(0, std::memory_order_relaxed);
     const int threads = c->copy_threads;
     std::atomic<int>* ready = c->chunk_ready;
-    const size_t* first = c->chunk_first;
+    const size_t* first = c->grid.chunk_first;
     const std::function<int(int)> copy_job = [=](int w) -> int {
         if (w >= threads) return 0;
         int faulted = 0;  // ranges whose share this thread has faulted in already
@@ -1474,7 +1288,7 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
         }
     };
     size_t largest = 0;
-    for (int j = 0; j < ranges; j++) largest = std::max(largest, c->chunk_first[j + 1] - c->chunk_first[j]);
+    for (int j = 0; j < ranges; j++) largest = std::max(largest, c->grid.chunk_first[j + 1] - c->grid.chunk_first[j]);
     const PipelineScratch sized(c, two_streams ? 2 : 1, largest);
     if (int r = compute_impl(c, p, device_reference_values, nullptr, nullptr, 1u, -1, ov)) return abort_copy(r);
     const double t_prep = trace ? since() : 0.0;
@@ -1484,22 +1298,22 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
     }
     // 2. per-voxel kernels, range by range, alternating between two streams (the next range fills the GPU while the
     //    last waves of the previous one drain); results go straight to the mapped staging buffer, or to HBM + DMA
-    float* out_base = dma ? c->d_out : c->d_staging;
+    float* out_base = dma ? c->grid.out.get() : c->grid.staging.device();
     {
         NarrowScope scope(c);
         for (int j = 0; j < ranges; j++) {
             const bool second = two_streams && !(j & 1);  // range 0 on the second stream
             scope.select_range(j, second ? 1 : 0);
             hipStream_t s = second ? c->stream2 : c->stream;
-            float* out = out_base + c->chunk_first[j];
+            float* out = out_base + c->grid.chunk_first[j];
             if (int r = compute_impl(c, p, nullptr, out, s, 2u, -1)) return abort_copy(r);
             if (p->flags & CRF_FLAG_ABSOLUTE_VALUE)
-                if (launch_abs(out, c->num_voxels, s) != hipSuccess) return abort_copy(fail(c, CRF_ERR_DEVICE, "launch_abs failed"));
+                if (launch_abs(out, c->view.num_voxels, s) != hipSuccess) return abort_copy(fail(c, CRF_ERR_DEVICE, "launch_abs failed"));
             if (hipEventRecord(c->chunk_done[j], s) != hipSuccess) return abort_copy(fail(c, CRF_ERR_DEVICE, "hipEventRecord failed"));
             if (dma) {
-                const size_t off = c->chunk_first[j], count = c->chunk_first[j + 1] - off;
+                const size_t off = c->grid.chunk_first[j], count = c->grid.chunk_first[j + 1] - off;
                 if (hipStreamWaitEvent(c->copy_stream, c->chunk_done[j], 0) != hipSuccess ||
-                    hipMemcpyAsync(c->h_staging + off, c->d_out + off, count * sizeof(float), hipMemcpyDeviceToHost,
+                    hipMemcpyAsync(c->grid.staging.host() + off, c->grid.out.get() + off, count * sizeof(float), hipMemcpyDeviceToHost,
                                    c->copy_stream) != hipSuccess ||
                     hipEventRecord(c->chunk_copied[j], c->copy_stream) != hipSuccess)
                     return abort_copy(fail(c, CRF_ERR_DEVICE, "enqueueing the copy of a result range failed"));
@@ -1512,7 +1326,7 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
         const hipError_t e = crf::spin_on_event(dma ? c->chunk_copied[j] : c->chunk_done[j]);
         if (e != hipSuccess) return abort_copy(fail(c, CRF_ERR_DEVICE, fmt("waiting for result range %d failed: %s", j, hipGetErrorString(e))));
         c->chunk_ready[j].store(1, std::memory_order_release);
-        if (trace) fprintf(stderr, "crf_compute: range %d (%zu voxels) landed at %.0f us\n", j, c->chunk_first[j + 1] - c->chunk_first[j], since());
+        if (trace) fprintf(stderr, "crf_compute: range %d (%zu voxels) landed at %.0f us\n", j, c->grid.chunk_first[j + 1] - c->grid.chunk_first[j], since());
     }
     c->copy_pool->wait();
     if (trace) fprintf(stderr, "crf_compute: copier pool started by %.0f us, preparation launched by %.0f us, launches issued by %.0f us, "
@@ -1530,7 +1344,7 @@ int crf_compute_device(crf_context* c, const crf_params* p, const void* device_r
     if (p && p->prepared_slot != 0) {
         if (p->prepared_slot < 0 || p->prepared_slot > CRF_PREPARED_SLOTS)
             return fail(c, CRF_ERR_ARGUMENT, fmt("prepared_slot %d outside [0,%d]", p->prepared_slot, CRF_PREPARED_SLOTS));
-        if (c && !c->d_prep_slots) return fail(c, CRF_ERR_STATE, "prepared_slot given but crf_prepare_device was never called");
+        if (c && !c->prep_slots) return fail(c, CRF_ERR_STATE, "prepared_slot given but crf_prepare_device was never called");
         if (int r = compute_impl(c, p, nullptr, device_out, stream, 2u, p->prepared_slot - 1)) return r;
     } else {
         if (int r = compute_impl(c, p, device_reference_values, device_out, stream, 3u, -1)) return r;
@@ -1584,11 +1398,11 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
     if (int r = ensure_wide(c, s)) return r;
     if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, num_requests))) return r;
     // two-field request mode: the j side reads the secondary members (CRF_FLAG_QUERY_FROM_SECONDARY)
-    const float* const* members_j = c->d_member_table;
+    const float* const* members_j = c->view.members;
     if (p->flags & CRF_FLAG_QUERY_FROM_SECONDARY) {
-        if (c->sec_members.empty())
+        if (c->grid.secondary.ptrs.empty())
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_QUERY_FROM_SECONDARY needs secondary members (crf_upload_secondary_members)");
-        members_j = c->d_sec_table;
+        members_j = c->view.secondary;
     }
     const crf::PairArgs a{p->measure, p->num_bins, p->k, (p->flags & CRF_FLAG_ABSOLUTE_VALUE) ? 1 : 0,
                           kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
@@ -1596,25 +1410,25 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
     hipError_t e = hipErrorNotSupported;
     const char* force_generic = getenv("CRF_REQUESTS_GENERIC");  // tuning / tests: the counting kernel
     if (!(force_generic && *force_generic == '1') && p->measure == CRF_PEARSON) {
-        e = crf::launch_pearson_requests(c->d_member_table, members_j, c->cs, c->xs, c->ys, c->num_voxels,
+        e = crf::launch_pearson_requests(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
                                          static_cast<const uint32_t*>(device_requests), num_requests, a.use_abs,
                                          static_cast<float*>(device_out), s);
         c->last_kernel = "pearson_request_kernel";
     } else if (!(force_generic && *force_generic == '1') && (p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC)) {
-        e = crf::launch_sorted_requests_binned(c->d_member_table, members_j, c->cs, c->xs, c->ys, c->num_voxels,
+        e = crf::launch_sorted_requests_binned(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
                                                static_cast<const uint32_t*>(device_requests), num_requests, p->measure,
-                                               p->num_bins, a.use_abs, c->d_tables, static_cast<float*>(device_out), s);
+                                               p->num_bins, a.use_abs, c->grid.tables.get(), static_cast<float*>(device_out), s);
         c->last_kernel = "sorted_request_kernel";
     } else if (!(force_generic && *force_generic == '1')) {
-        e = crf::launch_sorted_requests(c->d_member_table, members_j, c->cs, c->xs, c->ys, c->num_voxels,
+        e = crf::launch_sorted_requests(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
                                         static_cast<const uint32_t*>(device_requests), num_requests, p->measure,
                                         a.use_abs, static_cast<float*>(device_out), s);
         c->last_kernel = "sorted_request_kernel";
     }
     if (e == hipErrorNotSupported) {
-        e = crf::launch_pair_requests(c->d_member_table, members_j, c->cs, c->xs, c->ys, c->num_voxels,
-                                      static_cast<const uint32_t*>(device_requests), num_requests, a, c->d_tables,
-                                      c->scratch[0].workspace, static_cast<float*>(device_out), s);
+        e = crf::launch_pair_requests(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
+                                      static_cast<const uint32_t*>(device_requests), num_requests, a, c->grid.tables.get(),
+                                      c->grid.scratch[0].workspace.get(), static_cast<float*>(device_out), s);
         c->last_kernel = "pair_request_kernel";
     }
     return launch_status(c, e);
@@ -1632,20 +1446,13 @@ int crf_compute_requests(crf_context* c, const crf_params* p, const crf_request*
             return fail(c, CRF_ERR_ARGUMENT, fmt("request %zu addresses a voxel outside the grid", r));
     }
     if (int r = bind_device(c)) return r;
-    if (num_requests > c->request_capacity) {
-        if (c->d_requests) (void)hipFree(c->d_requests);
-        if (c->d_request_out) (void)hipFree(c->d_request_out);
-        c->d_requests = nullptr;
-        c->d_request_out = nullptr;
-        c->request_capacity = 0;
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_requests), num_requests * sizeof(crf_request)));
-        CRF_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_request_out), num_requests * sizeof(float)));
-        c->request_capacity = num_requests;
-    }
-    CRF_HIP(c, hipMemcpyAsync(c->d_requests, host_requests, num_requests * sizeof(crf_request), hipMemcpyHostToDevice,
+    CRF_HIP(c, c->requests.reserve(num_requests));
+    CRF_HIP(c, c->request_out.reserve(num_requests));
+    CRF_HIP(c, hipMemcpyAsync(c->requests.get(), host_requests, num_requests * sizeof(crf_request), hipMemcpyHostToDevice,
                               c->stream));
-    if (int r = crf_compute_requests_device(c, p, c->d_requests, num_requests, c->d_request_out, nullptr)) return r;
-    CRF_HIP(c, hipMemcpyAsync(host_out, c->d_request_out, num_requests * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (int r = crf_compute_requests_device(c, p, c->requests.get(), num_requests, c->request_out.get(), nullptr)) return r;
+    CRF_HIP(c, hipMemcpyAsync(host_out, c->request_out.get(), num_requests * sizeof(float), hipMemcpyDeviceToHost,
+                              c->stream));
     CRF_HIP(c, hipStreamSynchronize(c->stream));
     return CRF_OK;
 }
@@ -1659,9 +1466,9 @@ int crf_compute_ensemble_stat_device(crf_context* c, int stat, void* device_out,
     const bool native = native_reduction(c);
     return run_windowed(c, device_out, stream, native, [&](float* o, hipStream_t s, TimedLaunch& t) {
         if (native)
-            return crf::launch_ensemble_stat_narrow(stat, c->d_narrow_table, c->format, c->cs, c->num_voxels, o, s, t.e0,
+            return crf::launch_ensemble_stat_narrow(stat, c->view.narrow, c->grid.format, c->cs, c->view.num_voxels, o, s, t.e0,
                                                     t.e1, &t.info);
-        return crf::launch_ensemble_stat(stat, c->d_member_table, c->cs, c->num_voxels, o, s, t.e0, t.e1, &t.info);
+        return crf::launch_ensemble_stat(stat, c->view.members, c->cs, c->view.num_voxels, o, s, t.e0, t.e1, &t.info);
     });
 }
 
@@ -1678,9 +1485,9 @@ int crf_compute_set_predicate_device(crf_context* c, int op, float comparison_va
     const bool native = native_reduction(c);
     return run_windowed(c, device_out, stream, native, [&](float* o, hipStream_t s, TimedLaunch& t) {
         if (native)
-            return crf::launch_set_predicate_narrow(c->d_narrow_table, c->format, c->cs, c->num_voxels, op, comparison_value,
+            return crf::launch_set_predicate_narrow(c->view.narrow, c->grid.format, c->cs, c->view.num_voxels, op, comparison_value,
                                                     count_lower, count_upper, o, s, t.e0, t.e1, &t.info);
-        return crf::launch_set_predicate(c->d_member_table, c->cs, c->num_voxels, op, comparison_value, count_lower,
+        return crf::launch_set_predicate(c->view.members, c->cs, c->view.num_voxels, op, comparison_value, count_lower,
                                          count_upper, o, s, t.e0, t.e1, &t.info);
     });
 }
@@ -1704,12 +1511,12 @@ int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, v
     if (estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 && (k < 1 || k >= c->cs))
         return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be in [1, cs-1=%d]", k, c->cs - 1));
     if (int r = bind_device(c)) return r;
-    if (int r = ensure_workspace(c, crf::dkl_workspace_bytes(c->cs, estimator, num_bins, std::min(c->num_voxels, kWindowVoxels)))) return r;
+    if (int r = ensure_workspace(c, crf::dkl_workspace_bytes(c->cs, estimator, num_bins, std::min(c->view.num_voxels, kWindowVoxels)))) return r;
     // psi(n) = -gamma + H_{n-1} (boost::math::digamma at positive integers, DKL.cpp:156)
     const double knn_const =
         estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 ? psi_int(c->cs) - psi_int(k) + std::log(2.0) : 0.0;
     return run_windowed(c, device_out, stream, false, [&](float* o, hipStream_t s, TimedLaunch& t) {
-        return crf::launch_dkl(c->d_member_table, c->cs, c->num_voxels, estimator, num_bins, k, knn_const, c->scratch[0].workspace, o,
+        return crf::launch_dkl(c->view.members, c->cs, c->view.num_voxels, estimator, num_bins, k, knn_const, c->grid.scratch[0].workspace.get(), o,
                                s, t.e0, t.e1, &t.info);
     });
 }
@@ -1758,8 +1565,8 @@ int crf_take_kernel_time(crf_context* c, double* out_ms_sum, int* out_launches) 
         CRF_HIP(c, hipEventElapsedTime(&ms, p.first, p.second));
         sum += double(ms);
         n++;
-        c->ev_free.push_back(p.first);
-        c->ev_free.push_back(p.second);
+        c->ev_free.push_back(std::move(p.first));
+        c->ev_free.push_back(std::move(p.second));
     }
     c->ev_pending.clear();
     *out_ms_sum = sum;
@@ -1787,12 +1594,8 @@ int crf_members_changed(crf_context* c) {
     if (!c) return CRF_ERR_ARGUMENT;
     if (int r = bind_device(c)) return r;
     CRF_HIP(c, hipDeviceSynchronize());  // evaluations in flight may still read what is dropped
-    c->minmax_valid = false;
-    c->sec_minmax_valid = false;
-    c->host_chunks = 0;
-    c->windows = 0;
-    drop_packed(c);
-    drop_wide(c);
+    primary_members_changed(c);
+    secondary_members_changed(c);
     return CRF_OK;
 }
 

@@ -11,103 +11,124 @@
 
 #include "../../include/corrfield.h"
 #include "crf_internal.h"
+#include "crf_owned.h"
 #include "crf_pool.h"
 
 constexpr int kMaxHostChunks = 16;  // z-chunks of a host-output evaluation (kernel of chunk i+1 under the D2H of chunk i)
 
 // Scratch that the per-voxel kernels WRITE.  Launches that share a set must be ordered on one stream.
 struct crf_scratch {
-    uint32_t* todo = nullptr;  // deferred-voxel list of the split-sort rank kernels: a counter, then todo_voxels indices
-    size_t todo_voxels = 0;
-    unsigned char* workspace = nullptr;  // blockIdx-indexed voxel tiles / rank columns of the generic (cs > 128) kernels
-    size_t workspace_bytes = 0;
+    crf::DeviceBuffer<uint32_t> todo;  // deferred-voxel list of the split-sort rank kernels: a counter, then the indices
+    crf::DeviceBuffer<unsigned char> workspace;  // blockIdx-indexed voxel tiles / rank columns of the generic kernels
 };
 
-struct crf_context {
-    int device = -1;
-    hipStream_t stream = nullptr;  // the context's own stream (used when the caller passes none)
-    std::string err;
-    int xs = 0, ys = 0, zs = 0, cs = 0;
-    size_t num_voxels = 0;
-    // members
-    void* owned_block = nullptr;  // one allocation holding every uploaded member (stride owned_stride floats)
-    size_t owned_stride = 0;
-    std::vector<const float*> members;  // cs device pointers (owned or borrowed)
-    const float** d_member_table = nullptr;
-    int max_vpt = 1;
-    // primary members in a narrow native format (crf_upload_members_format / crf_bind_members_device_format): `narrow`
-    // holds the cs device pointers and `members` stays empty until a call that needs fp32 members builds the widened
-    // copy (api.cpp: ensure_wide), one owned block; the Pearson, the Kendall and (where routed: api.cpp native_binned) the binned-MI field at 2..128 members, the sibling
-    // reductions, the extrema and the reference gathers read `narrow` directly
+// cs member volumes on the device, in one element format.
+struct crf_member_set {
+    crf::DeviceBuffer<unsigned char> owned;  // uploaded members: one block, 256-byte aligned each; empty for bound ones
+    std::vector<const void*> ptrs;           // cs device pointers (into `owned`, the wide copy or the caller's memory);
+                                             //   empty: the set is not there
+    crf::DeviceBuffer<const void*> table;    // the same cs pointers on the device
     int format = CRF_MEMBER_F32;
-    void* narrow_owned_block = nullptr;
-    std::vector<const void*> narrow;
-    const void** d_narrow_table = nullptr;
-    bool narrow_aligned = false;       // every narrow pointer is 4-byte aligned (the native Pearson kernel loads dwords)
-    bool narrow_element_aligned = false;  // ... aligned to its element (the native Kendall and binned-MI kernels load elements)
-    void* wide_block = nullptr;        // the widened copy, lazily
-    int last_format = CRF_MEMBER_F32;  // what the per-voxel kernel of the last field evaluation read
-    // secondary members (second scalar field of the SEPARATE / SEPARATE_SYMMETRIC modes), optional
-    void* sec_owned_block = nullptr;
-    std::vector<const float*> sec_members;
-    const float** d_sec_table = nullptr;
-    bool sec_minmax_valid = false;
-    float sec_min_v = 0.f, sec_max_v = 0.f;
-    // scratch
-    float* d_ref = nullptr;    // cs reference values
-    float* d_prep = nullptr;   // crf::kPrepBytes
-    float* d_prep_slots = nullptr;  // CRF_PREPARED_SLOTS x crf::kPrepBytes, lazily (crf_prepare_device)
-    float* d_out = nullptr;    // num_voxels floats, lazily (crf_compute only)
-    double* d_tables = nullptr;  // psi / p ln p / noise tables for this member count (crf_internal.h)
+    bool minmax_valid = false;  // min_v / max_v hold the extrema of the current values
+    float min_v = 0.f, max_v = 0.f;
+    // what the set's consumers ask about the pointers (api.cpp: install_table)
+    int vpt = 1;                   // fp32: the widest vector load every member allows (4, 2 or 1 floats)
+    bool dword_aligned = false;    // narrow: every member is 4-byte aligned (the kernels that load dwords)
+    bool element_aligned = false;  // narrow: ... aligned to its element (the kernels that load single elements)
+    const float* f32(int m) const { return static_cast<const float*>(ptrs[size_t(m)]); }
+    const float* const* f32_table() const { return reinterpret_cast<const float* const*>(table.get()); }
+    void clear() {
+        owned.reset();
+        ptrs.clear();
+        minmax_valid = false;
+    }
+};
+
+// Everything whose size depends on the grid or the member count.  crf_set_grid replaces it with a fresh value; what is
+// derived from the members is dropped in one place (api.cpp: primary_members_changed and its siblings).
+struct crf_grid_state {
+    // The primary members are in `members` (format == CRF_MEMBER_F32) or in `narrow` (crf_upload_members_format /
+    // crf_bind_members_device_format with a narrow format).  With narrow members, `members` stays empty until an
+    // evaluation that has no native route needs fp32 values: then it points into `wide`, the converted copy
+    // (api.cpp: ensure_wide; native_field and native_reduction say which evaluations read `narrow` as it is).
+    crf_member_set members, narrow;
+    int format = CRF_MEMBER_F32;
+    crf::DeviceBuffer<float> wide;
+    crf_member_set secondary;  // second scalar field of the SEPARATE / SEPARATE_SYMMETRIC modes, optional, fp32
+    // packed copy of fp32 members for the Pearson field (crf_internal.h), built at the first Pearson field evaluation
+    // after the members change (api.cpp: ensure_packed)
+    crf::DeviceBuffer<unsigned char> packed;  // header, then body
+    int pack_state = 0;                       // 0: not decided for the current members, 1: packed, -1: declined
+    crf::DeviceBuffer<float> ref;      // cs reference values
+    crf::DeviceBuffer<float> out;      // the whole grid, lazily (host-output calls only)
+    crf::DeviceBuffer<double> tables;  // psi / p ln p / noise tables for this member count (crf_internal.h)
     // [0]: every launch on the context's stream or a caller's; [1]: the ranges of a host-output evaluation that run on
     // stream2.  Lazily; sized before the first launch of an evaluation, never between its ranges (api.cpp: ensure_todo).
     crf_scratch scratch[2];
-    int scratch_set = 0;         // the set the launch being issued uses (api.cpp: NarrowScope::select_range)
-    int pipeline_sets = 1;       // while crf_compute runs its range pipeline: the streams it uses, and the voxels of
-    size_t pipeline_voxels = 0;  //   its largest range (0: no pipeline, scratch is sized for num_voxels)
-    uint32_t* d_requests = nullptr;  // staging of host pair requests / their results, lazily
-    float* d_request_out = nullptr;
-    size_t request_capacity = 0;
-    uint32_t* d_minmax = nullptr;
-    bool minmax_valid = false;
-    // packed copy of the members for the Pearson field (crf_internal.h), built lazily at the first Pearson field
-    // evaluation after the members change (api.cpp: ensure_packed)
-    int member_layout = CRF_MEMBER_LAYOUT_AUTO;  // crf_set_member_layout
-    int pack_state = 0;                          // 0: not decided for the current members, 1: packed, -1: declined
-    unsigned char* d_packed = nullptr;           // header, then body (one allocation)
-    size_t packed_bytes = 0;
-    uint32_t* d_pack_fallbacks = nullptr;
-    int last_layout = CRF_MEMBER_LAYOUT_RAW;     // of the last Pearson field evaluation
-    float min_v = 0.f, max_v = 0.f;
-    // profiling
-    bool profiling = false;
-    std::vector<hipEvent_t> ev_free;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;
-    std::string last_kernel;
     // host-output evaluations (crf_compute): the grid in up to kMaxHostChunks voxel ranges, one member-pointer table per
     // range; the per-voxel kernel of a range stores into the pinned, device-mapped staging buffer and a pool of host
     // threads moves finished ranges into the caller's buffer (api.cpp: compute_to_host)
-    const float** d_chunk_tables = nullptr;  // host_chunks x cs pointers
-    int host_chunks = 0;                     // 0: tables not built for the current members
-    bool chunk_native = false;               // the tables hold the narrow pointers (native Pearson field), not fp32 ones
+    crf::DeviceBuffer<const void*> chunk_tables;  // host_chunks x cs pointers
+    int host_chunks = 0;                          // 0: tables not built for the current members
+    bool chunk_native = false;                    // the tables point into `narrow` (a native field), not into `members`
     size_t chunk_first[kMaxHostChunks + 1] = {};  // first voxel of every range; [host_chunks] = alloc_voxels
-    std::atomic<int> chunk_ready[kMaxHostChunks] = {};  // 1: range landed in the staging buffer, -1: evaluation failed
-    hipStream_t stream2 = nullptr;           // odd ranges (the next range fills the GPU while the previous one drains)
-    hipStream_t copy_stream = nullptr;       // DMA form only (CRF_HOST_PATH=dma, CRF_FLAG_ABSOLUTE_VALUE)
-    hipEvent_t prep_done = nullptr;
-    hipEvent_t chunk_done[kMaxHostChunks] = {};    // range evaluated
-    hipEvent_t chunk_copied[kMaxHostChunks] = {};  // DMA form: range landed in the staging buffer (copy stream)
-    float* h_staging = nullptr;                    // pinned + mapped, alloc_voxels floats, lazily
-    float* d_staging = nullptr;                    // its device address
-    std::unique_ptr<crf::SpinPool> copy_pool;      // copier threads, lazily
-    int copy_threads = 0;                          // how many of them a copy uses (calibrated at first use)
-    int copy_threads_cap = 0;                      // > 0: upper bound set by the owner (a device group shares the host)
+    crf::PinnedBuffer staging;                    // alloc_voxels floats, lazily
     // member volumes of 4 GiB or more: evaluated in windows (api.cpp: ensure_windows)
-    bool windowed = false;
-    const float** d_window_tables = nullptr;  // windows x (1 or 2) x cs pointers (primary [, secondary] members)
-    int windows = 0;                          // 0: tables not built for the current members
+    crf::DeviceBuffer<const float*> window_tables;  // windows x (1 or 2) x cs pointers (primary [, secondary] members)
+    int windows = 0;                                // 0: tables not built for the current members
     bool window_has_secondary = false;
-    size_t alloc_voxels = 0;  // voxels of the whole local grid (num_voxels is narrowed while a chunk is being launched)
+};
+
+// What a launch reads: the whole local grid (api.cpp: whole_view), or one window / one voxel range of it while a
+// NarrowScope is active.  Non-owning; the owners above are never repointed.
+struct crf_launch_view {
+    const float* const* members = nullptr;    // fp32 primary members
+    const float* const* secondary = nullptr;  // null: no secondary members
+    const void* const* narrow = nullptr;      // primary members in their narrow format
+    size_t num_voxels = 0;
+    int max_vpt = 1;
+    int scratch_set = 0;  // the crf_scratch the launch being issued writes
+};
+
+// Members are destroyed in reverse order of declaration, and crf_destroy relies on it: `stream` comes first because it
+// goes last (everything else was used on it), and `copy_pool` comes after `grid` because the copier threads are joined
+// before the staging buffer they read goes.  The device is bound before a context is deleted or re-gridded.
+struct crf_context {
+    int device = -1;
+    crf::Stream stream;  // the context's own stream (used when the caller passes none)
+    std::string err;
+    int xs = 0, ys = 0, zs = 0, cs = 0;
+    size_t alloc_voxels = 0;  // voxels of the whole local grid
+    bool windowed = false;    // member volumes of 4 GiB or more
+    crf_grid_state grid;
+    crf_launch_view view;
+    int last_format = CRF_MEMBER_F32;  // what the per-voxel kernel of the last field evaluation read
+    int member_layout = CRF_MEMBER_LAYOUT_AUTO;  // crf_set_member_layout
+    int last_layout = CRF_MEMBER_LAYOUT_RAW;     // of the last Pearson field evaluation
+    // context-lifetime device memory
+    crf::DeviceBuffer<float> prep;        // crf::kPrepBytes
+    crf::DeviceBuffer<float> prep_slots;  // CRF_PREPARED_SLOTS x crf::kPrepBytes, lazily (crf_prepare_device)
+    crf::DeviceBuffer<uint32_t> minmax;   // the two keys of the extrema kernels
+    crf::DeviceBuffer<uint32_t> pack_fallbacks;
+    crf::DeviceBuffer<crf_request> requests;  // staging of host pair requests / their results, lazily
+    crf::DeviceBuffer<float> request_out;
+    int pipeline_sets = 1;       // while crf_compute runs its range pipeline: the streams it uses, and the voxels of
+    size_t pipeline_voxels = 0;  //   its largest range (0: no pipeline, scratch is sized for the view's voxels)
+    // profiling
+    bool profiling = false;
+    std::vector<crf::Event> ev_free;
+    std::vector<std::pair<crf::Event, crf::Event>> ev_pending;
+    std::string last_kernel;
+    // the range pipeline of crf_compute (the range tables themselves are grid state)
+    std::atomic<int> chunk_ready[kMaxHostChunks] = {};  // 1: range landed in the staging buffer, -1: evaluation failed
+    crf::Stream stream2;      // odd ranges (the next range fills the GPU while the previous one drains)
+    crf::Stream copy_stream;  // DMA form only (CRF_HOST_PATH=dma, CRF_FLAG_ABSOLUTE_VALUE)
+    crf::Event prep_done;
+    crf::Event chunk_done[kMaxHostChunks];    // range evaluated
+    crf::Event chunk_copied[kMaxHostChunks];  // DMA form: range landed in the staging buffer (copy stream)
+    std::unique_ptr<crf::SpinPool> copy_pool;  // copier threads, lazily
+    int copy_threads = 0;                      // how many of them a copy uses (calibrated at first use)
+    int copy_threads_cap = 0;                  // > 0: upper bound set by the owner (a device group shares the host)
 };
 
 

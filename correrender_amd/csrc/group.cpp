@@ -473,7 +473,7 @@ int group_compute(crf_group* g, const crf_params* params, int count, float* cons
     }
     // the exchange reads another context's member table as fp32 (crf::RefOverride)
     for (int r = 0; r < g->n; r++)
-        if (g->ctx[size_t(r)]->format != CRF_MEMBER_F32)
+        if (g->ctx[size_t(r)]->grid.format != CRF_MEMBER_F32)
             return gfail(g, CRF_ERR_UNSUPPORTED,
                          fmt("device groups evaluate fp32 members only: the context of slot %d holds members in a narrow "
                              "native format (crf_bind_members_device_format)", r));

@@ -37,7 +37,7 @@ def binned_device(eng, ref=None, measure=MI, **kw):
 
 
 def routed_native(fmt, cs):
-    """The routing table of native_binned (crf_internal.h: binned_narrow_routed), from profiles/narrow_binned_ab.md."""
+    """The routing table of the native binned-MI field (api.cpp: native_field; crf_internal.h: binned_narrow_routed), from profiles/narrow_binned_ab.md."""
     n = (cs + 15) // 16 * 16
     return fmt == "u8" or (fmt == "u16" and n in (32, 64)) or (fmt == "f16" and n == 64)
 
