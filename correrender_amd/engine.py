@@ -463,8 +463,11 @@ class CorrField:
 
 class CorrFieldGroup:
     """Several GPUs behind one caller thread (crf_group_*): the whole grid in, the whole field out; the z-slab split,
-    the per-device worker threads and the reference-vector exchange (RCCL broadcast, or a peer copy when a device
-    ordinal repeats) live inside libcorrfield.  Mirrors CorrField.compute for host arrays."""
+    the per-device worker threads and the reference-vector exchange live inside libcorrfield.  The exchange is a direct
+    read of the owning device's members whenever every pair of devices has peer access (also when a device ordinal
+    repeats), else RCCL (ncclBroadcast, ncclAllReduce for a batch) when the ordinals are distinct, else staged peer
+    copies; CRF_GROUP_EXCHANGE=peer/rccl/copy forces a form and `exchange` names the one in use.  Mirrors
+    CorrField.compute for host arrays."""
 
     def __init__(self, devices: Sequence[int]):
         self._lib = load_library()
@@ -554,6 +557,13 @@ class CorrFieldGroup:
         del keep
         return out
 
+    def _check_slot_outputs(self, outs):
+        """outs[slot]: the device-resident result of one evaluation, one tensor per device slot."""
+        xs, ys, _ = self.grid
+        for slot, t in enumerate(outs):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() != xs * ys * self.slab(slot)[1]:
+                raise ValueError(f"output of slot {slot} must be a contiguous CUDA float32 tensor of the slab's size")
+
     def compute_device(self, measure, outs, ref=None, *, k=None, kraskov_estimator_index=1, num_bins=80, minmax_ref=None,
                        minmax_query=None, reference_values=None, symmetric=False, reference_from_secondary=False,
                        absolute_value=False):
@@ -563,12 +573,9 @@ class CorrFieldGroup:
         minmax_ref, minmax_query = CorrField._binned_ranges(self, measure, minmax_ref, minmax_query, mode)
         p, keep = CorrField._params(self, measure, ref, k, kraskov_estimator_index, num_bins, minmax_ref, minmax_query,
                                     reference_values, flags)
-        xs, ys, _ = self.grid
         if len(outs) != len(self.devices):
             raise ValueError("one output tensor per device slot")
-        for slot, t in enumerate(outs):
-            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() != xs * ys * self.slab(slot)[1]:
-                raise ValueError(f"output of slot {slot} must be a contiguous CUDA float32 tensor of the slab's size")
+        self._check_slot_outputs(outs)
         ptrs = (C.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
         self._check(self._lib.crf_group_compute_device(self._g, C.byref(p), ptrs))
         del keep
@@ -612,11 +619,8 @@ class CorrFieldGroup:
         n = len(self.devices)
         if len(outs) != len(arr) or any(len(row) != n for row in outs):
             raise ValueError("outs: one row of per-slot tensors per reference point")
-        xs, ys, _ = self.grid
         for row in outs:
-            for slot, t in enumerate(row):
-                if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() != xs * ys * self.slab(slot)[1]:
-                    raise ValueError(f"output of slot {slot} must be a contiguous CUDA float32 tensor of the slab's size")
+            self._check_slot_outputs(row)
         ptrs = (C.c_void_p * (len(arr) * n))(*[t.data_ptr() for row in outs for t in row])
         self._check(self._lib.crf_group_compute_batch_device(self._g, arr, len(arr), ptrs))
         del keep

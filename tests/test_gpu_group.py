@@ -1,6 +1,7 @@
 """GPU: the device group of the C ABI (crf_group_*) -- several z-slabs behind one caller thread.  On the 1-GPU box the
-group is rehearsed with a repeated device ordinal (two / three contexts on the same card, reference vector exchanged by
-the peer-copy path); a one-device group forced onto RCCL runs the real ncclBroadcast on a 1-rank communicator.  Every
+group is rehearsed with a repeated device ordinal (two, three or eight contexts on the same card; by default the reference
+values are then read directly out of the owning slab's members, and CRF_GROUP_EXCHANGE=copy rehearses the staged peer
+copies); a one-device group forced onto RCCL runs the real ncclBroadcast / ncclAllReduce on a 1-rank communicator.  Every
 result must be bit-identical to the single-context result (and so to the oracle)."""
 import os
 
@@ -215,3 +216,53 @@ def test_group_batch_equals_single_evaluations(engine, monkeypatch, exchange):
                              f"batch host, reference from the secondary field, {exchange} {ref}")
         with pytest.raises(ca.CorrFieldError, match="outside"):
             grp.compute_batch(Measure.PEARSON, [(0, 0, 0), (0, 0, zs)])
+
+
+@pytest.mark.parametrize("exchange", ["peer", "copy", "rccl1"])
+def test_group_is_regridded(engine, monkeypatch, exchange):
+    """One group through three grids: B has more members than A (the reference vector and the batch rows grow) and
+    another z-slice count (every slab moves); A again runs in the buffers that B left behind."""
+    import torch
+    devices = [0] if exchange == "rccl1" else [0, 0, 0]
+    n = len(devices)
+    monkeypatch.setenv("CRF_GROUP_EXCHANGE", "rccl" if exchange == "rccl1" else exchange)
+    grid_a, grid_b = (12, 6, 5, 8), (10, 4, 7, 24)
+    with ca.CorrFieldGroup(devices) as grp:
+        assert {"peer": "peer read", "copy": "peer copy", "rccl1": "rccl"}[exchange] in grp.exchange
+        for step, (xs, ys, zs, cs) in enumerate([grid_a, grid_b, grid_a]):
+            ens = synth.box_ensemble(xs, ys, zs, cs, seed=31 + step)
+            engine.set_grid(xs, ys, zs, cs)
+            engine.upload_members(ens)
+            grp.set_grid(xs, ys, zs, cs)
+            grp.upload_members(ens)
+            refs = [(1, 2, 0), (xs - 1, 0, zs // 2), (5, ys - 1, zs - 1)]     # with three slabs: one owner each
+            if n == 3:
+                slabs = [grp.slab(s) for s in range(n)]
+                assert all(z0 <= ref[2] < z0 + zn for ref, (z0, zn) in zip(refs, slabs))
+            for measure in (Measure.PEARSON, Measure.SPEARMAN):
+                want = [engine.compute(measure, ref).copy() for ref in refs]
+                what = f"grid {step} {exchange} {measure.name}"
+                assert_bit_exact(grp.compute(measure, refs[1]), want[1], f"{what} compute")
+                outs = [[torch.empty(xs * ys * grp.slab(s)[1], dtype=torch.float32, device="cuda") for s in range(n)]
+                        for _ in refs]
+                grp.compute_device(measure, outs[0], refs[2])
+                assert_bit_exact(torch.cat(outs[0]).cpu().numpy(), want[2], f"{what} compute_device")
+                grp.compute_batch_device(measure, refs, outs)
+                for ref, row, field in zip(refs, outs, want):
+                    assert_bit_exact(torch.cat(row).cpu().numpy(), field, f"{what} compute_batch_device {ref}")
+
+
+def test_partly_built_group_is_released(engine):
+    """The third context cannot be created (no such device: an error return): the two that exist are released with the
+    group, and the next group on the same card works."""
+    with pytest.raises(ca.CorrFieldError):
+        ca.CorrFieldGroup([0, 0, 99])
+    xs, ys, zs, cs = 12, 6, 5, 8
+    ens = synth.box_ensemble(xs, ys, zs, cs, seed=41)
+    engine.set_grid(xs, ys, zs, cs)
+    engine.upload_members(ens)
+    with ca.CorrFieldGroup([0, 0]) as grp:
+        grp.set_grid(xs, ys, zs, cs)
+        grp.upload_members(ens)
+        assert_bit_exact(grp.compute(Measure.PEARSON, (7, 3, 4)), engine.compute(Measure.PEARSON, (7, 3, 4)),
+                         "group created after a partly built one")
