@@ -376,7 +376,8 @@ __global__ __launch_bounds__(64) void mi_binned_hist_kernel(const float* const* 
         double mi = joint - sx;
 #pragma unroll 2
         for (int b = 0; b < nb; b++) mi -= tableT[hist_y[b * 64]];  // tableT[0] == 0
-        const bool slow = total != cs || !ref_all_valid;
+        // a voxel with a NaN member has total < cs too, but its result is NaN whatever the sum
+        const bool slow = (total != cs || !ref_all_valid) && !is_nan;
         if (slow) {
             // probabilities are c/total: direct evaluation, first occurrence of each bin / cell contributes its term
             mi = 0.0;

@@ -206,11 +206,68 @@ __device__ __forceinline__ double binned_mi_term(double mi, int cx, int cy, int 
     return mi;
 }
 
+constexpr int kPivotSelectMinK = 16;  // more neighbours than this: selection by pivots instead of kk minimum passes
+
+// The same value as the minimum passes below give, the kk-th smallest distance counted with multiplicity (infinity when
+// fewer than kk distances are numbers), by partitioning: the answer lies in (lo, hi), a pass counts the distances of
+// that interval below and at the pivot p and picks the next pivot on either side (the candidate with the smallest hash
+// of its index, so the member order does not matter): about 2 ln(cs) passes whatever kk is.
+template <class LoadX, class LoadY>
+__device__ __forceinline__ double kth_chebyshev_distance_by_pivots(int cs, int kk, int i, double pxi, double pyi,
+                                                                   LoadX px, LoadY py) {
+    const double inf = __longlong_as_double(0x7FF0000000000000ll);
+    double p = -1.0;  // distances are >= 0: -1 stands for "none"
+    for (int j = 0; j < cs && p < 0.0; j++) {
+        const double d = fmax(fabs(pxi - px(j)), fabs(pyi - py(j)));
+        if (j != i && d == d) p = d;
+    }
+    if (p < 0.0) return inf;
+    double lo = -1.0, hi = inf;
+    bool has_hi = false;
+    int need = kk;  // the answer is the need-th smallest distance above lo
+#pragma unroll 1
+    for (uint32_t pass = 1;; pass++) {
+        int c_lt = 0, c_eq = 0;
+        double a = -1.0, b = -1.0;
+        uint32_t ha = 0xFFFFFFFFu, hb = 0xFFFFFFFFu;
+#pragma unroll 4
+        for (int j = 0; j < cs; j++) {
+            const double d = fmax(fabs(pxi - px(j)), fabs(pyi - py(j)));
+            const bool in = j != i && d > lo && (!has_hi || d < hi);
+            const bool lt = in && d < p, gt = in && d > p;
+            c_lt += lt ? 1 : 0;
+            c_eq += (in && d == p) ? 1 : 0;
+            const uint32_t h = (uint32_t(j) + pass * 7919u) * 2654435761u;
+            if (lt && h <= ha) {
+                a = d;
+                ha = h;
+            }
+            if (gt && h <= hb) {
+                b = d;
+                hb = h;
+            }
+        }
+        if (need <= c_lt) {  // c_lt >= 1: a exists
+            hi = p;
+            has_hi = true;
+            p = a;
+        } else if (need <= c_lt + c_eq) {
+            return p;
+        } else {
+            if (b < 0.0) return inf;  // nothing above p: fewer than kk numbers (only without an upper bound)
+            need -= c_lt + c_eq;
+            lo = p;
+            p = b;
+        }
+    }
+}
+
 // Kraskov: Chebyshev distance from sample i = (pxi, pyi) to its kk-th neighbour, by repeated minimum passes (each pass
-// finds the smallest distance above the previous one and how many samples sit at it)
+// finds the smallest distance above the previous one and how many samples sit at it); many neighbours: by pivots
 template <class LoadX, class LoadY>
 __device__ __forceinline__ double kth_chebyshev_distance(int cs, int kk, int i, double pxi, double pyi, LoadX px,
                                                          LoadY py) {
+    if (kk > kPivotSelectMinK) return kth_chebyshev_distance_by_pivots(cs, kk, i, pxi, pyi, px, py);
     const double inf = __longlong_as_double(0x7FF0000000000000ll);
     double cur = -1.0, m = 0.0;
     int cnt = 0;

@@ -1001,7 +1001,9 @@ hipError_t launch_mi_kraskov(const float* const* d_members, int cs, size_t num_v
     return launch_field(plan, d_members, cs, num_voxels, ref, a, d_tables, d_prep, d_out, s, ev_begin, ev_end, info);
 }
 
-// any cs (tables must fit LDS: cs <= 2048), k <= 128; hipErrorNotSupported otherwise
+// more than 128 members: the tile-free kernel while its three tables of cs doubles fit LDS beside the partial sums
+// (kraskov_table_bytes(cs) + kDirectSumBytes <= 60 KiB, 24 cs + 20480 <= 61440: cs <= 1706) and min(k, cs - 1) <= 128;
+// hipErrorNotSupported otherwise (-> generic_kernel)
 hipError_t launch_mi_kraskov_direct(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                                     const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out,
                                     hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {

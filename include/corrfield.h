@@ -237,7 +237,9 @@ int crf_gather_reference_rows_device(crf_context* ctx, const int32_t* xyz, int n
 int crf_set_kraskov_noise(crf_context* ctx, const double* ref_noise, const double* query_noise);
 
 /* ---- evaluation (replaces the hot loop CorrelationCalculator.cpp:868-1142) ------------------------------- */
-/* Synchronous, host output: what calculateCpu(t, e, buffer) does.  host_out receives xs*ys*zs floats. */
+/* Synchronous, host output: what calculateCpu(t, e, buffer) does.  host_out receives xs*ys*zs floats.
+ * Member counts: the Pearson field (no CRF_FLAG_SYMMETRIC) takes any cs; every other measure and mode, here, in the
+ * *_device forms and in crf_compute_requests, takes at most 2048 members and returns CRF_ERR_UNSUPPORTED beyond. */
 int crf_compute(crf_context* ctx, const crf_params* params, float* host_out);
 /* Asynchronous, device output, stream-ordered, no host synchronisation: the form the multi-GPU path and the
  * benchmark use.  device_reference_values: DEVICE pointer to cs floats or NULL (then params->reference_values or

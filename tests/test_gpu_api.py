@@ -64,6 +64,9 @@ def test_member_count_limits_are_reported(engine):
         with pytest.raises(CorrFieldError) as e:
             engine.compute(m, (0, 0, 0))
         assert e.value.code == 4 and "at most" in e.value.message                     # CRF_ERR_UNSUPPORTED, says which
+    with pytest.raises(CorrFieldError) as e:
+        engine.dkl("binned")
+    assert e.value.code == 4 and "at most" in e.value.message
 
 
 def test_upload_and_bind_are_equivalent_and_state_is_reusable(engine):
@@ -131,7 +134,7 @@ def test_device_synth_generator_is_slab_consistent_and_follows_the_recipe(engine
 
 
 @pytest.mark.parametrize("measure", list(Measure))
-@pytest.mark.parametrize("cs", [16, 50, 150])
+@pytest.mark.parametrize("cs", [16, 50, 150, 1707])
 def test_prepared_slots_match_inline_preparation(measure, cs):
     """crf_prepare_device + prepared_slot (two-phase evaluation of the multi-GPU driver) == the one-call evaluation."""
     ens = synth.box_ensemble(12, 10, 6, cs, seed=cs)

@@ -79,6 +79,12 @@ CASES = [
     (FIELD, 100, 40, {}, "Direct K64 TI1"),
     (BEYOND_128, 160, 70, {}, "Direct K128 TI1"),
     (BEYOND_128, 200, 150, {}, "unsupported"),
+    # the three tables of cs doubles beside the 20480 bytes of partial sums: 61424 bytes at 1706 members, 61448 at 1707,
+    # against 60 KiB = 61440
+    (BEYOND_128, 1706, 3, {}, "Direct K3 TI8"),
+    (BEYOND_128, 1706, 128, {}, "Direct K128 TI1"),
+    (BEYOND_128, 1707, 3, {}, "unsupported"),
+    (BEYOND_128, 1707, 128, {}, "unsupported"),
     # CRF_KRASKOV_DIRECT=1 with _STAGE, _DXT, _TI4
     (FIELD, 20, 3, DIRECT, "Direct K3 TI4 dxt stage"),
     (FIELD, 20, 1, dict(DIRECT, stage=0), "Direct K1 TI8 dxt"),
@@ -113,6 +119,8 @@ CASES = [
     (SYMMETRIC, 100, 20, {}, "Direct K32 TI1"),
     (SYMMETRIC, 100, 64, {}, "Direct K64 TI1"),
     (SYMMETRIC, 100, 70, {}, "unsupported"),
+    (SYMMETRIC, 1706, 3, {}, "Direct K3 TI8"),
+    (SYMMETRIC, 1707, 3, {}, "unsupported"),
 ]
 
 
