@@ -222,7 +222,7 @@ int ensure_wide(crf_context* c, hipStream_t s) {
 }
 
 // Whether the per-voxel kernel of this field evaluation reads the narrow members as they are (view.narrow), no fp32 copy.
-// Everything else -- Kraskov MI, more than kNarrowMaxMembers members, the symmetric mode, windowed grids, pair requests --
+// Everything else -- more than kNarrowMaxMembers members, the symmetric mode, windowed grids, pair requests --
 // runs on the fp32 copy (ensure_wide).  Per measure:
 //   Pearson    2..128 members, dword loads: every member 4-byte aligned (kernels_pearson.hip: pearson_narrow_kernel)
 //   Kendall    2..128 members, element loads: the element's own alignment (kernels_rank_narrow.hip)
@@ -231,6 +231,9 @@ int ensure_wide(crf_context* c, hipStream_t s) {
 //              among the fp32 kernels only: it does not move a native call.
 //   binned MI  2..128 members where measured faster than the copy route (crf_internal.h: binned_narrow_routed;
 //              profiles/narrow_binned_ab.md); CRF_BINNED_HIST=1 asks for the histogram kernel, which reads fp32
+//   Kraskov MI 2..128 members, element loads, where measured no slower than the copy route (kraskov_plan.h:
+//              kraskov_narrow_plan; profiles/narrow_kraskov_ab.md).  The CRF_KRASKOV_* switches move a native call as they
+//              move an fp32 call; CRF_KRASKOV_SORTED=1 asks for the sorted-column kernel, which reads fp32
 bool native_field(const crf_context* c, const crf_params* p) {
     const crf_grid_state& g = c->grid;
     if (g.format == CRF_MEMBER_F32 || (p->flags & CRF_FLAG_SYMMETRIC) || c->cs > crf::kNarrowMaxMembers || c->windowed)
@@ -244,6 +247,8 @@ bool native_field(const crf_context* c, const crf_params* p) {
         case CRF_BINNED_MI_CC:
             if (const char* hv = getenv("CRF_BINNED_HIST"); hv && *hv == '1') return false;
             return c->cs >= 2 && g.narrow.element_aligned && crf::binned_narrow_routed(g.format, c->cs);
+        case CRF_MI_KRASKOV:
+        case CRF_KMI_CC: return g.narrow.element_aligned && crf::kraskov_narrow_routed(g.format, c->cs, p->k);
         default: return false;
     }
 }
@@ -808,6 +813,11 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
         case CRF_MI_KRASKOV:
         case CRF_KMI_CC: {
             const crf::KraskovArgs ka{p->k, est, p->measure == CRF_KMI_CC, kraskov_c_term(p->k, est)};
+            if (native) {  // Kraskov MI on narrow members: the reference side is fp32 as ever
+                e = crf::launch_mi_kraskov_narrow(c->view.narrow, c->grid.format, c->cs, c->view.num_voxels, ref, ka,
+                                                  c->grid.tables.get(), prep, out, s, e0, e1, info);
+                break;
+            }
             e = crf::launch_mi_kraskov(c->view.members, c->cs, c->view.num_voxels, ref, ka, c->grid.tables.get(), prep, out, s,
                                        e0, e1, info);
             break;

@@ -402,6 +402,19 @@ __device__ __forceinline__ float exact_div(float a, float b, float rcp) {
     return fmaf(rem, rcp, q0);
 }
 
+// The value the calculators see of ONE stored code that a kernel holds in a register (load_code_nt): narrow_value's
+// operations, the integer formats' quotient through exact_div with a compile-time reciprocal (an integer below 2^16 over
+// a constant denominator: its preconditions).
+template <int FMT>
+__device__ __forceinline__ float narrow_code_value(uint32_t code) {
+    if constexpr (FMT == CRF_MEMBER_F16) {
+        return float(__builtin_bit_cast(_Float16, uint16_t(code)));
+    } else {
+        constexpr float kDen = FMT == CRF_MEMBER_U8 ? 255.0f : 65535.0f;
+        return exact_div(float(code), kDen, 1.0f / kDen);  // == float(code) / kDen
+    }
+}
+
 // The voxel side of computePearson2<float> (Correlation.cpp:141-174) for one lane: y[0..cs) in registers, a_e =
 // invNm1 * ((x_e - meanX) / sdX) prepared once per evaluation.  Sequential fp32, no contraction.
 // SURE: slots 0..SURE-1 are members whatever cs is (the caller's contract), so only the slots behind them are guarded.

@@ -159,7 +159,8 @@ hipError_t launch_pack_members(const float* const* d_members, int cs, size_t num
 // The value the calculators see of a u8 / u16 / f16 element is float(b) / 255.0f, float(s) / 65535.0f, float(h)
 // (reference: src/Volume/Cache/HostCacheEntry.cpp:107-176).  The Pearson, the Kendall and the binned-MI field at
 // 2..kNarrowMaxMembers members read such members directly (kernels_pearson.hip: pearson_narrow_kernel;
-// kernels_rank_narrow.hip: kendall_narrow_kernel; kernels_binned_narrow.hip: mi_binned_narrow_kernel), and so do the
+// kernels_rank_narrow.hip: kendall_narrow_kernel; kernels_binned_narrow.hip: mi_binned_narrow_kernel), the Kraskov-MI field
+// where kraskov_narrow_plan routes it (kernels_kraskov_narrow.hip), and so do the
 // sibling reductions, the extrema and the gathers; everything else runs on an fp32 copy that launch_widen_members builds
 // (kernels_common.hip).
 constexpr int kNarrowMaxMembers = 128;
@@ -271,6 +272,17 @@ struct KraskovArgs {
 hipError_t launch_mi_kraskov(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                              const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
                              hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
+
+// ---- kernels_kraskov_narrow.hip: Kraskov MI on narrow members, read as stored --------------------------------------
+// 2 <= cs <= kNarrowMaxMembers where kraskov_narrow_plan (kraskov_plan.h) routes (format, cs, k) under the CRF_KRASKOV_*
+// switches in force -- kraskov_narrow_routed is that question; bit-identical to launch_mi_kraskov on the converted values.
+// d_narrow: cs device pointers to num_voxels elements of `format`, each aligned to its element (no more); num_voxels x
+// element size below kNarrowMaxBytes.  ref.values holds the cs reference values (fp32, any values) when ref.prepare();
+// d_prep gets launch_kraskov_prep's layout.  hipErrorInvalidValue for a combination that is not routed.
+bool kraskov_narrow_routed(int format, int cs, int k);
+hipError_t launch_mi_kraskov_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, const RefSource& ref,
+                                    const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out, hipStream_t s,
+                                    hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 
 hipError_t launch_mi_kraskov_direct(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,
                                     const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out,

@@ -27,17 +27,6 @@ namespace crf {
 
 enum BinnedNarrowMode { kBinTable = 0, kBinRcp = 1, kBinDiv = 2 };
 
-// the value the calculators see of a stored code (crf_device.h: narrow_value / narrow_pair, same operations)
-template <int FMT>
-__device__ __forceinline__ float narrow_code_value(uint32_t code) {
-    if constexpr (FMT == CRF_MEMBER_F16) {
-        return float(__builtin_bit_cast(_Float16, uint16_t(code)));
-    } else {
-        constexpr float kDen = FMT == CRF_MEMBER_U8 ? 255.0f : 65535.0f;
-        return exact_div(float(code), kDen, 1.0f / kDen);  // == float(code) / kDen (integer below 2^16, constant denominator)
-    }
-}
-
 // Everything behind the cell codes, for one lane = one voxel: mi_binned_kernel's lines (kernels_binned.hip), copied -- with
 // both kernels calling one function the fp32 kernel's instantiations come out with other register counts (-6 .. +5 VGPRs),
 // so its text stays as it is (profiles/narrow_binned_ab.md).  a[e] = b1 << 8 | b0 of slot e, kPadCode for a pad or a skipped

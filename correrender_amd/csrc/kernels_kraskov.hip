@@ -24,6 +24,7 @@
 
 #include "crf_device.h"
 #include "crf_internal.h"
+#include "crf_kraskov_device.h"
 #include "crf_mi_device.h"
 #include "kraskov_plan.h"
 
@@ -35,10 +36,7 @@ namespace crf {
 // prep (fp64 view): [0, cs) px_e = double(ref_e) + noise_ref_e (MutualInformation.cpp:417-420), member order;
 //                   [cs, 2cs) the same values sorted ascending (the reference sorts them for its 1-D range counts,
 //                   MutualInformation.cpp:187; voxel independent, so sorted once per evaluation)
-// the distance table lies in the preparation buffer behind the two coordinate vectors (up to 128 members: 133 KB)
-__host__ __device__ inline int dxt_offset(int cs) { return (2 * cs + 7) / 8 * 8; }  // in doubles
-static_assert(size_t(((2 * kDxtMaxMembers + 7) / 8 * 8) + 128 * 128) * sizeof(double) <= kPrepBytes - 16, "prep buffer");
-
+// (crf_kraskov_device.h: dxt_offset, where the distance table lies behind them)
 __global__ __launch_bounds__(256) void kraskov_prep_kernel(RefSource src, const float* const* __restrict__ members,
                                                            int cs, const double* __restrict__ noise_ref,
                                                            double* __restrict__ prep) {
@@ -64,64 +62,6 @@ __global__ __launch_bounds__(256) void kraskov_prep_kernel(RefSource src, const 
             double d = __longlong_as_double(0x7FF0000000000000ll);
             if (j < cs && i < cs) d = (i == j) ? __longlong_as_double(0x7FEFFFFFFFFFFFFFll) : fabs(px[i] - px[j]);
             table[idx] = d;
-        }
-    }
-}
-
-constexpr double kCountSlack = 1e-15;  // default_epsilon<double>::value, MutualInformation.cpp:163
-
-// fp64 min / max / Chebyshev distance as single instructions.  fmin()/fmax() make hipcc canonicalise each operand first
-// (an extra v_max_f64 x, x); the operands here are never signalling NaNs and the k-select only needs "one of the two".
-__device__ __forceinline__ double min_f64(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double max_f64(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double chebyshev_f64(double dx, double dy) {  // max(|dx|, |dy|)
-    double r;
-    asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(dx), "v"(dy));
-    return r;
-}
-
-__device__ __forceinline__ double chebyshev_f64_sx(double dy, double abs_dx_uniform) {  // max(|dy|, s): s in SGPRs
-    double r;
-    asm("v_max_f64 %0, |%1|, %2" : "=v"(r) : "v"(dy), "s"(abs_dx_uniform));
-    return r;
-}
-
-// #{ t : tab[t] < v } for an ascending table of n entries; top = largest power of two <= n.  Branch-free binary search;
-// the table is shared by the wave (LDS), the probe index is per lane.
-__device__ __forceinline__ int count_less(const double* tab, int n, int top, double v) {
-    int pos = 0;
-    for (int step = top; step >= 1; step >>= 1) {
-        const int idx = pos + step;
-        const int probe = idx <= n ? idx : n;  // keep the read in range; the result is discarded when idx > n
-        pos = (idx <= n && tab[probe - 1] < v) ? idx : pos;
-    }
-    return pos;
-}
-
-// The same search for NCH bounds at once: the steps are the outer loop, so a step issues NCH independent LDS reads before
-// it waits (one search after the other is a chain of log2(n) dependent LDS round trips each -- and the && above
-// compiles to exec-masked branches; at 8 points x 2 bounds per sweep that latency was as long as the k-select itself).
-template <int NCH>
-__device__ __forceinline__ void count_less_batch(const double* tab, int n, int top, const double (&v)[NCH],
-                                                 int (&pos)[NCH]) {
-#pragma unroll
-    for (int c = 0; c < NCH; c++) pos[c] = 0;
-#pragma unroll 1
-    for (int step = top; step >= 1; step >>= 1) {
-#pragma unroll
-        for (int c = 0; c < NCH; c++) {
-            const int idx = pos[c] + step;
-            const bool ok = idx <= n;
-            const double val = tab[(ok ? idx : n) - 1];
-            pos[c] = (ok & (val < v[c])) ? idx : pos[c];
         }
     }
 }
@@ -318,13 +258,8 @@ __global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __re
 // the occupancy at 1.5 waves per SIMD).
 // SYM (symmetric field mode): the X side is voxel dependent too -- x_e = members_x[e][v] + noise_ref[e] (prep_px then
 // points at the noise_ref table), X counts by comparison like the Y counts instead of the binary search.
-// Occupancy the register allocator is held to (waves per SIMD): what the instantiations reached before the work split
-// below was added; left to itself the compiler now settles one step lower for K <= 2 and <8, 4>.
-constexpr int direct_min_waves(int K, int TI, bool SYM) {
-    if (SYM) return K <= 8 ? 2 : (K <= 32 ? 3 : 2);
-    return K <= 2 ? 4 : (K == 3 ? 3 : (K == 4 ? 2 : (K <= 32 ? 3 : 1)));
-}
-
+// (crf_kraskov_device.h: direct_min_waves, the occupancy the register allocator is held to.)
+//
 // STAGE (not SYM, share mode): the block copies a tile's cs x 64 values into LDS once (each wave fetches every fourth
 // member, non-temporal) and every sweep of every wave reads them from there -- one HBM / L2 read per value instead of
 // 2 cs / TI + 1 reads served by L1 / L2 (measured at the fabric counters: 1.18x the algorithmic bytes at 4 points per sweep).
@@ -924,23 +859,6 @@ DirectKernel direct_kernel(const KraskovPlan& p) {
         case 3: return direct_table_kernel_k<3>(p);
         default: return direct_table_kernel_k<4>(p);
     }
-}
-
-struct KraskovTables {
-    const double *psi, *noise_ref, *noise_query;
-};
-KraskovTables kraskov_tables(const double* d_tables, int cs) {
-    const double* noise_ref = d_tables + 2 * (cs + 1);
-    return {d_tables, noise_ref, noise_ref + cs};
-}
-
-KraskovSwitches read_switches() {  // at every call: the tests set them after the library is loaded
-    auto first_char = [](const char* name) {
-        const char* e = getenv(name);
-        return !e ? -1 : *e == '0' ? 0 : *e == '1' ? 1 : 2;
-    };
-    return {first_char("CRF_KRASKOV_SORTED"), first_char("CRF_KRASKOV_DIRECT"), first_char("CRF_KRASKOV_TILE"),
-            first_char("CRF_KRASKOV_DXT"),    first_char("CRF_KRASKOV_TI4"),    first_char("CRF_KRASKOV_STAGE")};
 }
 
 // kraskov_direct_kernel: 256 lanes; one block per group of four voxel tiles up to 65536 blocks (r01 capped the grid at

@@ -79,6 +79,44 @@ inline bool kraskov_field_plan(int cs, int k, bool direct_only, const KraskovSwi
     return true;
 }
 
+// Members stored as uint8, uint16 or float16 (format 1, 2, 3 of crf_member_format; 0 is fp32): whether the field runs
+// on them as stored (kernels_kraskov_narrow.hip) and, if so, with which plan -- the field plan's family, K, TI and dxt,
+// so that the native call adds its fp64 partial sums in the fp32 call's order under every switch setting.  false: the
+// call runs on the fp32 copy.  The routed set is the "within rule" column of profiles/narrow_kraskov_ab.md: a cell
+// (format, family, member count rounded up to 16, K) is routed only where the native kernel's time was within the fp32
+// kernel's on the copy plus its run-to-run spread at every measured member count of the cell -- for the tile-free kernel
+// at one count whose sweeps divide evenly among the four waves of a block and at one where they do not.  Cells that were
+// not measured stay on the copy, as does the Sorted family (CRF_KRASKOV_SORTED=1).  K = min(k, members - 1) up to 4, then
+// 8 for 5..8.  The K = 16 instantiation spills to scratch on narrow members as it does on fp32 and is therefore not built;
+// K = 32, 64, 128 were not measured.  What passed (member counts):
+//   uint8     column kernel K = 2, 3: 33..48;  tile-free kernel K = 2: 49..64, K = 3: 49..96, K = 4: 113..128,
+//             K = 8: 49..64 and 113..128
+//   uint16    tile-free kernel K = 2, 3: 49..64, K = 4 and K = 8: 113..128
+//   float16   tile-free kernel K = 2: 49..64, K = 3: 49..64 and 113..128, K = 4: 113..128, K = 8: 49..64 and 113..128
+constexpr int kKraskovNarrowMaxMembers = 128;
+struct KraskovNarrowCells {  // [K - 1] for K = 1..4, then K = 8; bit n - 1: member counts 16 n - 15 .. 16 n
+    unsigned column[4], direct[5];
+};
+constexpr KraskovNarrowCells kKraskovNarrowCells[4] = {
+    {{0, 0, 0, 0}, {0, 0, 0, 0, 0}},                    // fp32
+    {{0, 0x04, 0x04, 0}, {0, 0x08, 0x38, 0x80, 0x88}},  // uint8
+    {{0, 0, 0, 0}, {0, 0x08, 0x08, 0x80, 0x80}},        // uint16
+    {{0, 0, 0, 0}, {0, 0x08, 0x88, 0x80, 0x88}},        // float16
+};
+
+inline bool kraskov_narrow_plan(int format, int cs, int k, const KraskovSwitches& sw, KraskovPlan* p) {
+    if (format < 1 || format > 3 || cs < 2 || cs > kKraskovNarrowMaxMembers) return false;
+    KraskovPlan plan;
+    if (!kraskov_field_plan(cs, k, false, sw, &plan) || plan.family == KraskovFamily::Sorted) return false;
+    if (plan.K > 8 || (plan.family == KraskovFamily::Column && plan.K > 4)) return false;
+    const KraskovNarrowCells& cells = kKraskovNarrowCells[format];
+    const unsigned mask = plan.family == KraskovFamily::Column ? cells.column[plan.K - 1]
+                                                                : cells.direct[plan.K <= 4 ? plan.K - 1 : 4];
+    if (!(mask >> ((cs + 15) / 16 - 1) & 1u)) return false;
+    *p = plan;
+    return true;
+}
+
 // Symmetric field mode (kraskov_direct_kernel<K, TI, SYM>), 2 <= cs; false: k > 64 or the tables are beyond LDS.
 inline bool kraskov_symmetric_plan(int cs, int k, KraskovPlan* p) {
     const int kk = kraskov_kk(cs, k);

@@ -123,8 +123,9 @@ class CorrField:
         a plain [cs, n] uint8 or 16-bit tensor do only when n * itemsize is a multiple of 4.  Otherwise every per-voxel
         evaluation, the Pearson field, ensemble_stat and set_predicate included, runs on the fp32 copy (cs * n floats of
         device memory; last_member_format() says "f32", wide_copy_bytes() its size) -- pad the row stride, or use
-        upload_members, whose copy is aligned.  The native Kendall, Spearman and binned-MI fields (2..128 members; Spearman:
-        33..128; binned MI: uint8 at any of these counts, uint16 at 17..32 and 49..64, float16 at 49..64, else the copy)
+        upload_members, whose copy is aligned.  The native Kendall, Spearman, binned-MI and Kraskov-MI fields (2..128 members; Spearman:
+        33..128; binned MI: uint8 at any of these counts, uint16 at 17..32 and 49..64, float16 at 49..64, else the copy;
+        Kraskov MI: at the (format, member count, k) listed in include/corrfield.h, else the copy)
         load single elements and
         ask for the element's own alignment only, which every torch tensor has; member_minmax and the reference gathers
         need no alignment."""
@@ -149,13 +150,13 @@ class CorrField:
 
     def last_member_format(self) -> str:
         """The format the per-voxel kernel of the last field evaluation read: the members' own when the Pearson, the
-        Kendall or the binned-MI field read narrow members natively, "f32" when it ran on fp32 members or on the fp32 copy of narrow
+        Kendall, the Spearman, the binned-MI or the Kraskov-MI field read narrow members natively, "f32" when it ran on fp32 members or on the fp32 copy of narrow
         ones."""
         return MEMBER_FORMATS[self._lib.crf_last_member_format(self._ctx)]
 
     def wide_copy_bytes(self) -> int:
         """Bytes of the fp32 copy of narrow members that the context holds right now (0: none).  The Pearson, the
-        Kendall and (at the counts named under bind_members) the binned-MI field at 2..128 members, ensemble_stat, set_predicate, member_minmax and the reference gathers read
+        Kendall and (at the counts named under bind_members) the binned-MI and the Kraskov-MI field at 2..128 members, the Spearman field at 33..128 members, ensemble_stat, set_predicate, member_minmax and the reference gathers read
         narrow members as stored and never build it; every other evaluation does, at its first call."""
         return int(self._lib.crf_wide_copy_bytes(self._ctx))
 

@@ -165,18 +165,32 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *     becomes its bin through a 256-entry table that each block fills from min_query, max_query and num_bins, a 16-bit
  *     code through the arithmetic of the fp32 kernel on its value); crf_last_member_format then returns the narrow
  *     format.  Alignment and reference side as for the Kendall field.
+ *   - The Kraskov mutual-information field (CRF_MI_KRASKOV, CRF_KMI_CC without CRF_FLAG_SYMMETRIC; KSG-1 and KSG-2) reads
+ *     the narrow members directly where that was measured to be no slower than the copy route
+ *     (mi_kraskov_narrow_kernel, kraskov_direct_narrow_kernel: one byte / short load per member, the converted values or
+ *     the codes parked in LDS, every operation behind them the fp32 kernel's in the fp32 kernel's order):
+ *       (K = min(k, members - 1); "column plan": the LDS-column kernel, by default k = 2 up to 44 members, k = 3 up to 40)
+ *       uint8    K = 2, 3 at 33..48 members under a column plan; K = 2 at 49..64, K = 3 at 49..96, K = 4 at 113..128,
+ *                k = 5..8 at 49..64 and 113..128 members;
+ *       uint16   K = 2, 3 at 49..64 members; K = 4 and k = 5..8 at 113..128;
+ *       float16  K = 2 at 49..64, K = 3 at 49..64 and 113..128, K = 4 at 113..128, k = 5..8 at 49..64 and 113..128 members;
+ *     every other (format, member count, k) takes the fp32 copy, as does CRF_KRASKOV_SORTED=1 where it selects the
+ *     sorted-column kernel; the other CRF_KRASKOV_* switches move a native call as they move an fp32 call.
+ *     crf_last_member_format then returns the narrow format.  Alignment and reference side as for the Kendall field;
+ *     crf_set_kraskov_noise applies as on fp32 members.
  *   - The sibling reductions (crf_compute_ensemble_stat[_device], crf_compute_set_predicate[_device]) read the narrow
  *     members directly at any member count (ensemble_stat_narrow_kernel, set_predicate_narrow_kernel, reported by
  *     crf_last_kernel_name; crf_last_member_format speaks of field evaluations only and is left alone).  Like the
  *     Pearson field they load whole dwords, so borrowed members that are not all 4-byte aligned take the fp32 copy.
  *   - crf_member_minmax and the reference gathers (crf_gather_reference, crf_gather_reference_device,
  *     crf_gather_reference_rows_device) read the narrow members directly, whatever their alignment.
- *   - Everything else -- Spearman at 2..32 members, Kraskov mutual information, DKL, symmetric and pair-request evaluations, and the
- *     Pearson, Spearman, Kendall and binned-MI fields above 128 members (binned MI also at the counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
+ *   - Everything else -- Spearman at 2..32 members, DKL, symmetric and pair-request evaluations, and the
+ *     Pearson, Spearman, Kendall, binned-MI and Kraskov-MI fields above 128 members (binned MI and Kraskov MI also at the
+ *     counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
  *     call that needs it (one owned block of cs x xs*ys*zs floats; CRF_ERR_DEVICE naming the copy and its size if it
  *     cannot be allocated) and drops in crf_set_grid, upload, bind and crf_members_changed; crf_last_member_format then
  *     returns CRF_MEMBER_F32.  So do the Pearson field and the sibling reductions over borrowed members that are not all
- *     4-byte aligned.  A context that only runs the entry points of the six items above never builds the copy;
+ *     4-byte aligned.  A context that only runs the entry points of the seven items above never builds the copy;
  *     crf_wide_copy_bytes tells.
  *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.  Secondary members are fp32 only.
  *     crf_group_* evaluations on a context that holds narrow members: CRF_ERR_UNSUPPORTED.
@@ -191,11 +205,11 @@ enum crf_member_format { /* a tag only: the function crf_member_format() below s
 int crf_upload_members_format(crf_context* ctx, int format, const void* const* host_members);
 int crf_bind_members_device_format(crf_context* ctx, int format, const void* const* device_members);
 int crf_member_format(const crf_context* ctx);      /* format of the bound primary members */
-/* format the per-voxel kernel of the last field evaluation read: the members' own after a native Pearson, Kendall
- * or binned-MI field, CRF_MEMBER_F32 after anything that ran on fp32 members or on the fp32 copy */
+/* format the per-voxel kernel of the last field evaluation read: the members' own after a native Pearson, Kendall,
+ * Spearman, binned-MI or Kraskov-MI field, CRF_MEMBER_F32 after anything that ran on fp32 members or on the fp32 copy */
 int crf_last_member_format(const crf_context* ctx);
-/* bytes of the fp32 copy of narrow members held right now; 0 if none or ctx == NULL (the native Pearson, Kendall and
- * binned-MI fields, the sibling reductions, the extrema and the gathers never build it) */
+/* bytes of the fp32 copy of narrow members held right now; 0 if none or ctx == NULL (the native Pearson, Kendall,
+ * Spearman, binned-MI and Kraskov-MI fields, the sibling reductions, the extrema and the gathers never build it) */
 size_t crf_wide_copy_bytes(const crf_context* ctx);
 /* min of per-member minima / max of per-member maxima over the local grid (CorrelationCalculator.cpp:822-829 on
  * top of VolumeData::getMinMaxScalarFieldValue, VolumeData.cpp:1632-1670); computed on the device, cached until
