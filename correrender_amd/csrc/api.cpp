@@ -260,6 +260,14 @@ bool native_reduction(const crf_context* c) {
     return c->grid.format != CRF_MEMBER_F32 && c->grid.narrow.dword_aligned && !c->windowed;
 }
 
+// DKL reads narrow members element by element (kernels_dkl_narrow.hip: dkl_narrow_kernel; the element's own alignment), at
+// any member count, where that was measured to be no slower than dkl_kernel on the copy (crf_internal.h: dkl_narrow_routed;
+// profiles/narrow_dkl_ab.md).  CRF_DKL_COUNTING_SORT and CRF_DKL_BLOCKS_PER_CU move a native call as they move an fp32 call.
+bool native_dkl(const crf_context* c, int estimator, int k) {
+    return c->grid.format != CRF_MEMBER_F32 && c->grid.narrow.element_aligned && !c->windowed &&
+           crf::dkl_narrow_routed(c->grid.format, c->cs, estimator, k);
+}
+
 // Packs the members for the Pearson field if the layout policy asks for it (include/corrfield.h: crf_member_layout),
 // once per set of members, on stream s.  *use: the packed copy is there for this evaluation.
 int ensure_packed(crf_context* c, hipStream_t s, crf::PackedMembers* use) {
@@ -920,7 +928,7 @@ int ensure_host_ranges(crf_context* c, bool native) {
 
 // The ensemble-stat, set-predicate and DKL device calls: launch(out, stream, timed launch) once, or once per window of
 // a >= 4 GiB grid (stopping at the first window that fails), as one timed launch.  native: the launch reads the members in
-// their narrow format (native_reduction: never windowed), so no fp32 copy is built.
+// their narrow format (native_reduction, and DKL where dkl_narrow_routed says so: never windowed), so no fp32 copy is built.
 template <class Launch>
 int run_windowed(crf_context* c, void* device_out, void* stream, bool native, Launch&& launch) {
     if (int r = bind_device(c)) return r;
@@ -1525,7 +1533,11 @@ int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, v
     // psi(n) = -gamma + H_{n-1} (boost::math::digamma at positive integers, DKL.cpp:156)
     const double knn_const =
         estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 ? psi_int(c->cs) - psi_int(k) + std::log(2.0) : 0.0;
-    return run_windowed(c, device_out, stream, false, [&](float* o, hipStream_t s, TimedLaunch& t) {
+    const bool native = native_dkl(c, estimator, k);
+    return run_windowed(c, device_out, stream, native, [&](float* o, hipStream_t s, TimedLaunch& t) {
+        if (native)
+            return crf::launch_dkl_narrow(c->view.narrow, c->grid.format, c->cs, c->view.num_voxels, estimator, num_bins, k, knn_const,
+                                          c->grid.scratch[0].workspace.get(), o, s, t.e0, t.e1, &t.info);
         return crf::launch_dkl(c->view.members, c->cs, c->view.num_voxels, estimator, num_bins, k, knn_const, c->grid.scratch[0].workspace.get(), o,
                                s, t.e0, t.e1, &t.info);
     });

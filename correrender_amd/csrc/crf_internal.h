@@ -336,6 +336,29 @@ size_t dkl_workspace_bytes(int cs, int estimator, int num_bins, size_t num_voxel
 hipError_t launch_dkl(const float* const* d_members, int cs, size_t num_voxels, int estimator, int num_bins, int k,
                       double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s, hipEvent_t ev_begin,
                       hipEvent_t ev_end, LaunchInfo* info);
+// ---- kernels_dkl_narrow.hip: DKL on narrow members, read as stored ---------------------------------------------------
+// Any cs in 1..kMaxGenericMembers, both estimators, bit-identical to launch_dkl on the converted values; the workspace is
+// launch_dkl's (dkl_workspace_bytes: the columns hold converted floats).  d_narrow: cs device pointers to num_voxels
+// elements of `format`, each aligned to its element (no more); num_voxels x element size below kNarrowMaxBytes.  One event
+// pair around the one kernel, reported as "dkl_narrow_kernel".  hipErrorInvalidValue for CRF_MEMBER_F32 or an unknown format.
+// Which (format, member count, estimator, k) the native kernel serves, by measurement (profiles/narrow_dkl_ab.md: native
+// kernel time <= the fp32 kernel's on the copy + its run-to-run spread in every measured row of a class; a class is a
+// format, an estimator and an instantiation -- N = the member count rounded up to 16, or the counting sort).  The network
+// instantiations came out 1-5 % slower than dkl_kernel almost everywhere, the counting-sort ones 0-3 % faster:
+//   binned   uint8 and uint16 at N = 32 (17..32 members); uint8 and float16 from 97 members on (counting sort)
+//   k-NN     uint8 and uint16 at N = 64 (49..64 members) with k <= 2 (the register descent; larger k was not measured);
+//            every format from 129 members on (counting sort)
+// Everything else, the instantiations that were not measured (N = 16, 48, 80, 96) included, stays on the copy.
+constexpr bool dkl_narrow_routed(int format, int cs, int estimator, int k) {
+    if (format != CRF_MEMBER_U8 && format != CRF_MEMBER_U16 && format != CRF_MEMBER_F16) return false;
+    const int n = (cs + 15) / 16 * 16;
+    if (estimator == CRF_DKL_BINNED)
+        return cs >= 97 ? format != CRF_MEMBER_U16 : (n == 32 && format != CRF_MEMBER_F16);
+    return cs >= 129 || (n == 64 && k <= 2 && format != CRF_MEMBER_F16);
+}
+hipError_t launch_dkl_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, int estimator, int num_bins,
+                             int k, double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s,
+                             hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 
 // pair-request mode (kernels_generic.hip): requests = 8 uint32 each {xi,yi,zi,i,xj,yj,zj,j}; voxel i is read from
 // d_members_i, voxel j from d_members_j.  d_requests == nullptr: request r = voxel pair (r, r) (symmetric field mode).

@@ -67,8 +67,9 @@ crf_context* EnsembleReduceCalculator::residentContext(int timeStepIdx, int ense
                                                        ensembleAxis ? c : ensembleIdx));
     // Members that all share one narrow native format go to the device as they are stored, like CorrelationCalculator's
     // (crf_member_format: half or a quarter of the bytes cross the bus and stay resident, no float view is converted on
-    // the host, and the mean, spread and set predicate read them at that width); members of mixed formats take the
-    // float views.
+    // the host, and the mean, spread and set predicate read them at that width, as does DKL at the member counts where
+    // that is no slower than its fp32 kernel -- include/corrfield.h lists them; elsewhere DKL runs on the context's fp32
+    // copy); members of mixed formats take the float views.
     const ScalarDataFormat native = entries[0]->getScalarDataFormatNative();
     bool sameFormat = true;
     for (const HostCacheEntry& entry : entries) sameFormat = sameFormat && entry->getScalarDataFormatNative() == native;

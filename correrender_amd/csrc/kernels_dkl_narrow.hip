@@ -1,41 +1,32 @@
-// kernels_dkl.hip -- DKLCalculator on gfx950: the Kullback-Leibler divergence between the
-// normalised distribution of a voxel's cs member values and N(0,1), two estimators
-//   binned        computeDKLBinned<double>       (src/Calculators/DKL.cpp:38-84)
-//   entropy k-NN  computeDKLKNNEstimate<double>  (src/Calculators/DKL.cpp:98-165; Kozachenko-Leonenko entropy)
-// driven like DKLCalculator::calculateCpu (src/Calculators/DKLCalculator.cpp:134-262): cs == 1 -> 1, NaN member -> NaN.
+// kernels_dkl_narrow.hip -- DKLCalculator on members stored as uint8, uint16 or float16, read as stored: dkl_narrow_kernel,
+// the sibling of dkl_kernel (kernels_dkl.hip, which describes the estimators and the mapping).
 //
-// Same mapping as the generic kernels (kernels_generic.hip): one lane = one voxel, the voxel's values in a per-lane
-// column [member][lane] of a tile in LDS (or, when it does not fit, in a global workspace slice owned by the persistent
-// block).  fp64 moments in member order exactly like the reference; the k-NN estimator sorts by counting (O(cs^2)
-// compares) and then plays the reference's step-halving window descent (KnnWindow below) in fp32.  4*cs + 4 algorithmic bytes
-// per voxel; VALU/LDS bound.  fp64 log/exp come from the device math library (<= 1 ulp from the host's): results agree
-// with the CPU restatement to ~1e-15 before the cast to float (tolerance 1e-5 relative, tests/test_gpu_dkl.py).
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
-
+// A lane owns one voxel and loads one byte / short per member (load_code_nt: non-temporal, the element's own alignment);
+// the code becomes the value the calculators see through narrow_code_value (crf_device.h: the correctly rounded
+// float(b) / 255.0f, float(s) / 65535.0f, float(h)), and from there on every operation is dkl_kernel's, in its order, on
+// that fp32 value: the LDS / workspace column holds converted floats, so the results are bit-identical to dkl_kernel's on
+// the converted values and tile sizes, workspace and grid sizing are the fp32 kernel's (crf_dkl_device.h).
+//
+// The kernel is a copy of dkl_kernel's text with another front end (FMT: the load, the element size behind the byte
+// offsets).  One body for both, inlined into each kernel, was tried first: every dkl_kernel<NS> came out with other
+// instructions than before, and the fp32 kernels have to stay what they are (the same happened to the binned-MI and
+// Kraskov kernels, profiles/narrow_binned_ab.md).  Whoever changes the arithmetic or its order in kernels_dkl.hip has to make
+// the same change here: tests/test_gpu_narrow_dkl.py compares the two bit for bit.
 #include "crf_device.h"
 #include "crf_dkl_device.h"
 #include "crf_internal.h"
 
 namespace crf {
 
-size_t dkl_workspace_bytes(int cs, int estimator, int num_bins, size_t num_voxels) {
-    const size_t tile = dkl_tile_bytes(cs, estimator, num_bins);
-    if (tile <= kDklLdsLimit) return 0;
-    const size_t tiles = (num_voxels + 63) / 64;
-    return tile * (tiles < size_t(kDklBlocks) ? tiles : size_t(kDklBlocks));
-}
-
-// knn_const = psi(cs) - psi(k) + ln 2, half_log_two_pi = 0.5 * double(std::log(float TWO_PI)): host libm, fp64
-// NS: size of the sorting network of the k-NN estimator's column sort (a multiple of 16 >= cs, at most 128), or 0: sort by
-// counting (any member count; also the instantiation the binned estimator runs).  One kernel per network size -- all
-// eight networks inside one kernel cost 512 registers and scratch.
-template <int NS>
-__global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(const float* const* __restrict__ members, float* __restrict__ out,
-                                                 size_t num_voxels, int cs, int estimator, int num_bins, int k,
-                                                 double knn_const, double half_log_two_pi,
-                                                 unsigned char* __restrict__ workspace) {
+// NS as for dkl_kernel: the sorting-network size (16, 32, ..., 128) or 0 (counting sort, any member count).
+// num_voxels x element size is below kNarrowMaxBytes (checked at upload / bind), so no byte offset wraps and
+// kOutOfRangeOffset stays past the end of every member: a padded slot reads code 0, value 0, as dkl_kernel's reads 0.0f.
+template <int FMT, int NS>
+__global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_narrow_kernel(
+    const void* const* __restrict__ members, float* __restrict__ out, size_t num_voxels, int cs, int estimator, int num_bins,
+    int k, double knn_const, double half_log_two_pi, unsigned char* __restrict__ workspace) {
+    static_assert(FMT == CRF_MEMBER_U8 || FMT == CRF_MEMBER_U16 || FMT == CRF_MEMBER_F16, "a narrow format");
+    constexpr uint32_t kElement = FMT == CRF_MEMBER_U8 ? 1u : 2u;
     extern __shared__ __align__(16) unsigned char smem[];
     // LDS: [ln(h), h = 0..cs, of the binned estimator (dkl_log_table_bytes)] [the tile, unless it lives in the workspace]
     double* s_logn = reinterpret_cast<double*>(smem);
@@ -53,7 +44,7 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
     float* vals = reinterpret_cast<float*>(tile) + lane;
     float* sorted = kInPlace ? vals : vals + size_t(cs) * 64;                                  // k-NN
     uint16_t* hist = reinterpret_cast<uint16_t*>(tile + size_t(cs) * 64 * sizeof(float)) + lane;  // binned
-    const uint32_t bytes = uint32_t(num_voxels) * 4u;
+    const uint32_t bytes = uint32_t(num_voxels) * kElement;
     const size_t tiles = (num_voxels + 63) / 64;
     const float qnan = __uint_as_float(0x7FC00000u);
     const double factor = 1.0 / double(cs);
@@ -61,7 +52,7 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
     for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const size_t v = t * 64 + lane;
         const bool active = v < num_voxels;
-        const uint32_t byte_offset = active ? uint32_t(v) * 4u : kOutOfRangeOffset;
+        const uint32_t byte_offset = active ? uint32_t(v) * kElement : kOutOfRangeOffset;
         bool is_nan = false;
         double mean = 0.0;
         double variance = 0.0;
@@ -72,8 +63,13 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
             int cs_p = cs;  // (laundered per phase: keeps the compiler from carrying NS uniform member-count tests as
             asm volatile("" : "+s"(cs_p));  // SGPR pairs across the persistent tile loop)
 #pragma unroll
-            for (int e = 0; e < NS; e++)
-                x[e] = load_member_nt(members[e < cs_p ? e : cs_p - 1], bytes, e < cs_p ? byte_offset : kOutOfRangeOffset);
+            for (int e = 0; e < NS; e++) {
+                x[e] = narrow_code_value<FMT>(load_code_nt<FMT>(members[e < cs_p ? e : cs_p - 1], bytes, e < cs_p ? byte_offset : kOutOfRangeOffset));
+                // float(h) is one v_cvt, and with the conversion visible to the later phases the float16 instantiations
+                // came out with 180 / 244 VGPRs at NS = 32 / 48 against dkl_kernel's 149 / 197, and 180 B of scratch at NS =
+                // 64.  Behind the empty asm the phases see an opaque fp32 value, as dkl_kernel's do: the same registers.
+                if constexpr (FMT == CRF_MEMBER_F16) asm("" : "+v"(x[e]));
+            }
             asm volatile("" : "+s"(cs_p));
 #pragma unroll
             for (int e = 0; e < NS; e++) {
@@ -93,7 +89,7 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
         } else {
 #pragma unroll 4
             for (int e = 0; e < cs; e++) {
-                const float xe = load_member_nt(members[e], bytes, byte_offset);
+                const float xe = narrow_code_value<FMT>(load_code_nt<FMT>(members[e], bytes, byte_offset));
                 is_nan |= xe != xe;
                 vals[e * 64] = xe;
                 mean += factor * double(xe);
@@ -359,21 +355,33 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
 }
 
 namespace {
-struct DklKernels {
-    using Member = float;
-    static constexpr const char* name = "dkl_kernel";
+template <int FMT>
+struct DklNarrowKernels {
+    using Member = void;
+    static constexpr const char* name = "dkl_narrow_kernel";
     template <int NS>
     static constexpr auto instance() {
-        return &dkl_kernel<NS>;
+        return &dkl_narrow_kernel<FMT, NS>;
     }
 };
 }  // namespace
 
-hipError_t launch_dkl(const float* const* d_members, int cs, size_t num_voxels, int estimator, int num_bins, int k,
-                      double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s, hipEvent_t ev_begin,
-                      hipEvent_t ev_end, LaunchInfo* info) {
-    return launch_dkl_family<DklKernels>(d_members, cs, num_voxels, estimator, num_bins, k, knn_const, d_workspace, d_out,
-                                         s, ev_begin, ev_end, info);
+hipError_t launch_dkl_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, int estimator, int num_bins,
+                             int k, double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s,
+                             hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    if (format != CRF_MEMBER_U8 && format != CRF_MEMBER_U16 && format != CRF_MEMBER_F16) return hipErrorInvalidValue;
+    if (num_voxels * member_format_bytes(format) >= kNarrowMaxBytes) return hipErrorInvalidValue;
+    switch (format) {
+        case CRF_MEMBER_U8:
+            return launch_dkl_family<DklNarrowKernels<CRF_MEMBER_U8>>(d_narrow, cs, num_voxels, estimator, num_bins, k, knn_const,
+                                                                      d_workspace, d_out, s, ev_begin, ev_end, info);
+        case CRF_MEMBER_U16:
+            return launch_dkl_family<DklNarrowKernels<CRF_MEMBER_U16>>(d_narrow, cs, num_voxels, estimator, num_bins, k, knn_const,
+                                                                       d_workspace, d_out, s, ev_begin, ev_end, info);
+        default:
+            return launch_dkl_family<DklNarrowKernels<CRF_MEMBER_F16>>(d_narrow, cs, num_voxels, estimator, num_bins, k, knn_const,
+                                                                       d_workspace, d_out, s, ev_begin, ev_end, info);
+    }
 }
 
 }  // namespace crf

@@ -127,7 +127,9 @@ class CorrField:
         33..128; binned MI: uint8 at any of these counts, uint16 at 17..32 and 49..64, float16 at 49..64, else the copy;
         Kraskov MI: at the (format, member count, k) listed in include/corrfield.h, else the copy)
         load single elements and
-        ask for the element's own alignment only, which every torch tensor has; member_minmax and the reference gathers
+        ask for the element's own alignment only, which every torch tensor has, and so does dkl where it reads the members
+        natively (binned: uint8 and uint16 at 17..32 members, uint8 and float16 from 97 on; k-NN: uint8 and uint16 at 49..64
+        with k <= 2, every format from 129 on; else the copy); member_minmax and the reference gathers
         need no alignment."""
         tensors = [members[i] for i in range(self.cs)]
         formats = {_member_format(t.dtype) for t in tensors}
@@ -156,7 +158,7 @@ class CorrField:
 
     def wide_copy_bytes(self) -> int:
         """Bytes of the fp32 copy of narrow members that the context holds right now (0: none).  The Pearson, the
-        Kendall and (at the counts named under bind_members) the binned-MI and the Kraskov-MI field at 2..128 members, the Spearman field at 33..128 members, ensemble_stat, set_predicate, member_minmax and the reference gathers read
+        Kendall and (at the counts named under bind_members) the binned-MI and the Kraskov-MI field at 2..128 members, the Spearman field at 33..128 members, ensemble_stat, set_predicate, dkl (at the counts named under bind_members), member_minmax and the reference gathers read
         narrow members as stored and never build it; every other evaluation does, at its first call."""
         return int(self._lib.crf_wide_copy_bytes(self._ctx))
 

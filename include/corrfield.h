@@ -182,15 +182,23 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *     members directly at any member count (ensemble_stat_narrow_kernel, set_predicate_narrow_kernel, reported by
  *     crf_last_kernel_name; crf_last_member_format speaks of field evaluations only and is left alone).  Like the
  *     Pearson field they load whole dwords, so borrowed members that are not all 4-byte aligned take the fp32 copy.
+ *   - DKL (crf_compute_dkl[_device]) reads the narrow members directly where that was measured to be no slower than the
+ *     copy route (dkl_narrow_kernel, reported by crf_last_kernel_name: one byte / short load per member, every operation
+ *     behind it the fp32 kernel's in the fp32 kernel's order, so the result is bit-identical to the copy route's):
+ *       binned estimator   uint8 and uint16 at 17..32 members; uint8 and float16 at 97..2048 members;
+ *       k-NN estimator     uint8 and uint16 at 49..64 members with k <= 2; every format at 129..2048 members;
+ *     every other (format, member count, estimator, k) takes the fp32 copy.  It loads single elements, so it asks for the
+ *     element's own alignment only, as the Kendall field does.  CRF_DKL_COUNTING_SORT and CRF_DKL_BLOCKS_PER_CU move a
+ *     native call as they move an fp32 call.  Like the other sibling reductions it leaves crf_last_member_format alone.
  *   - crf_member_minmax and the reference gathers (crf_gather_reference, crf_gather_reference_device,
  *     crf_gather_reference_rows_device) read the narrow members directly, whatever their alignment.
- *   - Everything else -- Spearman at 2..32 members, DKL, symmetric and pair-request evaluations, and the
- *     Pearson, Spearman, Kendall, binned-MI and Kraskov-MI fields above 128 members (binned MI and Kraskov MI also at the
- *     counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
+ *   - Everything else -- Spearman at 2..32 members, symmetric and pair-request evaluations, and the
+ *     Pearson, Spearman, Kendall, binned-MI and Kraskov-MI fields above 128 members (binned MI, Kraskov MI and DKL also at
+ *     the counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
  *     call that needs it (one owned block of cs x xs*ys*zs floats; CRF_ERR_DEVICE naming the copy and its size if it
  *     cannot be allocated) and drops in crf_set_grid, upload, bind and crf_members_changed; crf_last_member_format then
  *     returns CRF_MEMBER_F32.  So do the Pearson field and the sibling reductions over borrowed members that are not all
- *     4-byte aligned.  A context that only runs the entry points of the seven items above never builds the copy;
+ *     4-byte aligned.  A context that only runs the entry points of the eight items above never builds the copy;
  *     crf_wide_copy_bytes tells.
  *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.  Secondary members are fp32 only.
  *     crf_group_* evaluations on a context that holds narrow members: CRF_ERR_UNSUPPORTED.
@@ -209,7 +217,8 @@ int crf_member_format(const crf_context* ctx);      /* format of the bound prima
  * Spearman, binned-MI or Kraskov-MI field, CRF_MEMBER_F32 after anything that ran on fp32 members or on the fp32 copy */
 int crf_last_member_format(const crf_context* ctx);
 /* bytes of the fp32 copy of narrow members held right now; 0 if none or ctx == NULL (the native Pearson, Kendall,
- * Spearman, binned-MI and Kraskov-MI fields, the sibling reductions, the extrema and the gathers never build it) */
+ * Spearman, binned-MI and Kraskov-MI fields, the sibling reductions, DKL where it is read natively, the extrema and the
+ * gathers never build it) */
 size_t crf_wide_copy_bytes(const crf_context* ctx);
 /* min of per-member minima / max of per-member maxima over the local grid (CorrelationCalculator.cpp:822-829 on
  * top of VolumeData::getMinMaxScalarFieldValue, VolumeData.cpp:1632-1670); computed on the device, cached until
