@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "crf_context.h"
+#include "crf_host_copy.h"
 #include "crf_internal.h"
 
 namespace {
@@ -604,31 +605,11 @@ int ref_voxel(crf_context* c, int x, int y, int z, size_t* voxel) {
 // Range sizes are staggered over two streams so that kernel ends alternate and the last copy is small (ensure_host_ranges).
 // CRF_HOST_PATH=dma keeps results in HBM and copies each range with the DMA engine instead (also used when a post-pass
 // has to read the result back: CRF_FLAG_ABSOLUTE_VALUE).
-constexpr int kMadvPopulateWrite = 23;  // MADV_POPULATE_WRITE (Linux 5.14), not in every libc header
-constexpr size_t kPage = 4096;
-
+// The host half -- range partition, thread shares, pre-faulting, the copier loop -- is crf_host_copy.h (no HIP in it:
+// tests/native/host_copy.cpp runs it against a scripted producer).
 int env_int_or(const char* name, int fallback) {
     const char* v = getenv(name);
     return (v && *v) ? atoi(v) : fallback;
-}
-
-// faults [lo, hi) of the caller's buffer in (write access); mode 0: leave it to the copy, 1: touch, 2: populate
-void fault_in(char* base, size_t lo, size_t hi, int mode) {
-    if (mode == 0 || lo >= hi) return;
-    const uintptr_t a = (reinterpret_cast<uintptr_t>(base) + lo) & ~(kPage - 1);
-    const uintptr_t e = (reinterpret_cast<uintptr_t>(base) + hi + kPage - 1) & ~(kPage - 1);
-    if (mode == 2 && madvise(reinterpret_cast<void*>(a), e - a, kMadvPopulateWrite) == 0) return;
-    // fallback / mode 1: one write per page.  The bytes written are inside the caller's buffer and are overwritten by
-    // the result afterwards.
-    for (size_t off = lo; off < hi; off += kPage) static_cast<volatile char*>(base)[off] = 0;
-    static_cast<volatile char*>(base)[hi - 1] = 0;
-}
-
-// thread w's share of byte range [r_lo, r_hi) among `workers` threads, split on page boundaries
-void thread_share(size_t r_lo, size_t r_hi, int w, int workers, size_t* lo, size_t* hi) {
-    const size_t per = (((r_hi - r_lo) + size_t(workers) - 1) / size_t(workers) + kPage - 1) & ~(kPage - 1);
-    *lo = std::min(r_hi, r_lo + size_t(w) * per);
-    *hi = std::min(r_hi, *lo + per);
 }
 
 int ensure_copy_pool(crf_context* c) {
@@ -655,7 +636,7 @@ int ensure_copy_pool(crf_context* c) {
             c->copy_pool->run([&](int w) -> int {
                 if (w >= t) return 0;
                 size_t lo, hi;
-                thread_share(0, bytes, w, t, &lo, &hi);
+                crf::thread_share(0, bytes, w, t, &lo, &hi);
                 if (lo < hi) memcpy(dst.data() + lo, src + lo, hi - lo);
                 return 0;
             });
@@ -872,41 +853,10 @@ int ensure_host_ranges(crf_context* c, bool native) {
     if (g.host_chunks > 0 && g.chunk_native == native) return CRF_OK;
     g.host_chunks = 0;
     const size_t n = c->alloc_voxels;
-    std::vector<size_t> first{0};
-    const int forced = env_int_or("CRF_HOST_CHUNKS", 0);
-    if (forced >= 1) {  // experiments: equal ranges
-        size_t per = (n + size_t(forced) - 1) / size_t(forced);
-        per = (per + 1023) & ~size_t(1023);
-        for (size_t at = per; at < n && int(first.size()) < kMaxHostChunks; at += per) first.push_back(at);
-    } else {
-        // Shares of 64, consecutive ranges alternating between two streams: 3 6 6 6 6 6 6 6 6 5 4 2 2.  The two streams'
-        // kernels run concurrently and share the link; with the FIRST range half the size of the others the kernel ends
-        // alternate (B0 A0 B1 A1 ...), so results land every ~1/11 of the run from early on, the copier threads always
-        // have a landed range to move, and the last ranges are small: only their copy is not hidden behind a kernel.
-        // Same-process A/B at 256^3 (tools/measure_host_path.py ab, profiles/r03_host_boundary_variants.txt), resident /
-        // fresh destination: 13 ranges 1.326 / 1.391 ms; 11 ranges (4 8x6 6 3 2 1) 1.336 / 1.452; 8 staggered ranges
-        // 1.369 / 1.467; 8 shrinking ranges 16 14 11 8 6 4 3 2 (pairs end together) 1.378 / 1.527; 8 equal 1.450 / 1.644.
-        std::vector<int> kShares = {3, 6, 6, 6, 6, 6, 6, 6, 6, 5, 4, 2, 2};
-        if (const char* e = getenv("CRF_HOST_SHARES")) {  // experiments: comma-separated shares of 64
-            std::vector<int> v;
-            int sum = 0;
-            for (const char* q = e; *q;) {
-                v.push_back(atoi(q));
-                sum += v.back();
-                while (*q && *q != ',') q++;
-                if (*q == ',') q++;
-            }
-            if (sum == 64 && v.size() >= 1 && v.size() <= size_t(kMaxHostChunks)) kShares = v;
-        }
-        size_t acc = 0;
-        for (int j = 0; j + 1 < int(kShares.size()); j++) {
-            acc += size_t(kShares[size_t(j)]);
-            const size_t at = (n / 64 * acc + 1023) & ~size_t(1023);
-            if (at > first.back() && at < n) first.push_back(at);
-        }
-    }
-    const int ranges = int(first.size());
-    first.push_back(n);
+    // experiments: CRF_HOST_CHUNKS equal ranges, or CRF_HOST_SHARES comma-separated shares of 64
+    const std::vector<size_t> first = crf::host_range_partition(n, env_int_or("CRF_HOST_CHUNKS", 0),
+                                                                crf::parse_shares(getenv("CRF_HOST_SHARES")), kMaxHostChunks);
+    const int ranges = int(first.size()) - 1;
     std::vector<const void*> table(size_t(ranges) * size_t(c->cs));
     const crf_member_set& set = native ? g.narrow : g.members;
     const size_t element = crf::member_format_bytes(set.format);
@@ -1263,24 +1213,7 @@ int compute_to_host(crf_context* c, const crf_params* p, const void* device_refe
     std::atomic<int>* ready = c->chunk_ready;
     const size_t* first = c->grid.chunk_first;
     const std::function<int(int)> copy_job = [=](int w) -> int {
-        if (w >= threads) return 0;
-        int faulted = 0;  // ranges whose share this thread has faulted in already
-        for (int j = 0; j < ranges; j++) {
-            size_t lo, hi;
-            while (ready[j].load(std::memory_order_acquire) == 0) {
-                if (faulted < ranges) {
-                    thread_share(first[faulted] * sizeof(float), first[faulted + 1] * sizeof(float), w, threads, &lo, &hi);
-                    fault_in(dst, lo, hi, fault_mode);
-                    faulted++;
-                } else {
-                    _mm_pause();
-                }
-            }
-            if (ready[j].load(std::memory_order_acquire) < 0) return 0;  // the evaluation failed: nothing to copy
-            thread_share(first[j] * sizeof(float), first[j + 1] * sizeof(float), w, threads, &lo, &hi);
-            if (lo < hi) memcpy(dst + lo, src + lo, hi - lo);
-        }
-        return 0;
+        return crf::copy_ranges(dst, src, first, ranges, threads, ready, fault_mode, w);
     };
     c->copy_pool->start(copy_job);
     const double t_pool = trace ? since() : 0.0;

@@ -10,11 +10,10 @@
 #include <vector>
 
 #include "../../include/corrfield.h"
+#include "crf_host_copy.h"  // kMaxHostChunks
 #include "crf_internal.h"
 #include "crf_owned.h"
 #include "crf_pool.h"
-
-constexpr int kMaxHostChunks = 16;  // z-chunks of a host-output evaluation (kernel of chunk i+1 under the D2H of chunk i)
 
 // Scratch that the per-voxel kernels WRITE.  Launches that share a set must be ordered on one stream.
 struct crf_scratch {

@@ -14,7 +14,11 @@ The mask voxels (all members equal) are compared with the oracle's own answer, n
 Pearson / Spearman / Kendall, parity.assert_close for the MI estimators.  Binned MI of a constant column is H - H in fp64,
 a pure summation-order residue: measured on the MI355X, the kernels return 0.0 on all 456 mask voxels where the oracle
 returns 1.08e-15 or 6.4e-16 (161 members, 150 bins) and -3.6e-16 (16 members, 80 bins) -- the 1e-16-level difference of
-fp64 sums that kernels_binned.hip documents.  Kraskov MI agrees with the oracle bit for bit on them."""
+fp64 sums that kernels_binned.hip documents.  Kraskov MI agrees with the oracle bit for bit on them.
+
+The host half (crf_host_copy.h) has its own switches -- fault mode, huge pages, range count, copier threads -- and its own
+edge, the caller's destination (never touched, resident, not page-aligned): each goes through the checked evaluation once,
+on the 16-member Pearson control."""
 import re
 
 import numpy as np
@@ -110,8 +114,9 @@ def _sample(range_lengths):
 
 
 def _evaluate_checked(engine, oracle, data, capfd, monkeypatch, measure, om, *, exact=True, kw=None, okw=None, env=None,
-                      ref_values=None, kernel=None, expect=lambda f: f, what=""):
-    """One checked evaluation (module docstring); returns the host field."""
+                      ref_values=None, kernel=None, expect=lambda f: f, what="", out=None, ranges=None, copier_threads=None):
+    """One checked evaluation (module docstring); returns the host field.
+    out: the caller's destination (default: a new array); ranges, copier_threads: what the trace must report."""
     kw, okw = dict(kw or {}), dict(okw or {})
     what = f"{what or measure.name} cs={data.cs}"
     # 1. poison the staging buffer
@@ -123,7 +128,11 @@ def _evaluate_checked(engine, oracle, data, capfd, monkeypatch, measure, om, *, 
     capfd.readouterr()
     where = dict(reference_values=ref_values) if ref_values is not None and "reference_from_secondary" not in kw else {}
     ref = None if where else REF
+    if out is not None:
+        kw["out"] = out
     host = engine.compute(measure, ref, **where, **kw).reshape(-1)
+    kw.pop("out", None)
+    assert out is None or np.shares_memory(host, out)
     trace = capfd.readouterr().err
     host_kernel = engine.last_kernel_name()
     monkeypatch.delenv("CRF_HOST_TRACE")
@@ -135,6 +144,10 @@ def _evaluate_checked(engine, oracle, data, capfd, monkeypatch, measure, om, *, 
     assert [int(j) for j, _ in landed] == list(range(len(landed)))
     lengths = [int(v) for _, v in landed]
     assert sum(lengths) == N
+    if ranges is not None:
+        assert len(landed) == ranges, f"{what}: {len(landed)} ranges:\n{trace}"
+    if copier_threads is not None:
+        assert f"({len(landed)} ranges, {copier_threads} copier threads)" in trace, f"{what}:\n{trace}"
     # 4. the device path, one launch
     dev = torch.full((N,), -7.0, dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
@@ -239,6 +252,78 @@ def test_ranged_scratch_free_controls(engine, oracle, capfd, monkeypatch, name):
     else:
         _evaluate_checked(engine, oracle, data, capfd, monkeypatch, Measure.MUTUAL_INFORMATION_KRASKOV,
                           oracle_lib.MI_KRASKOV, exact=False, kw=dict(k=3), okw=dict(k=3))
+
+
+# ---- the host half's switches (crf_host_copy.h), each through the real pipeline once -----------------------------------
+# The 16-member Pearson control: no scratch, the least GPU work per case.  Which copier finds which range landed already
+# is a matter of timing here; tests/test_host_copy.py scripts those schedules on the CPU.
+SENTINEL = np.float32(-3.0)
+
+
+def _destination(kind):
+    """(out, check): the array handed to compute and what must hold of its surroundings afterwards."""
+    if kind == "fresh":
+        return np.empty(N, dtype=np.float32), lambda: None
+    if kind == "written":
+        return np.full(N, SENTINEL, dtype=np.float32), lambda: None
+    assert kind == "page_plus_4"
+    whole = np.full(N + 4096, SENTINEL, dtype=np.float32)
+    start = (-whole.ctypes.data % 4096) // 4 + 1
+    out = whole[start:start + N]
+    assert out.ctypes.data % 4096 == 4 and out.flags["C_CONTIGUOUS"]
+
+    def untouched_around():
+        assert (whole[:start] == SENTINEL).all() and (whole[start + N:] == SENTINEL).all(), "written outside the destination"
+    return out, untouched_around
+
+
+@pytest.mark.parametrize("destination", ["fresh", "written", "page_plus_4"])
+@pytest.mark.parametrize("fault", ["0", "1", "2"])
+def test_ranged_host_fault_modes_and_destinations(engine, oracle, capfd, monkeypatch, fault, destination):
+    """CRF_HOST_FAULT 0 (the copy faults the pages in), 1 (touched ahead), 2 (populated ahead) into a never-touched
+    array, a resident one, and one that starts one float past a page boundary inside a larger array."""
+    data = _data(engine, 16)
+    out, check = _destination(destination)
+    host = _evaluate_checked(engine, oracle, data, capfd, monkeypatch, Measure.PEARSON, oracle_lib.PEARSON, out=out,
+                             env={"CRF_HOST_FAULT": fault}, what=f"Pearson, CRF_HOST_FAULT={fault}, {destination} destination")
+    assert host.ctypes.data == out.ctypes.data
+    check()
+
+
+def test_ranged_host_no_huge_pages(engine, oracle, capfd, monkeypatch):
+    data = _data(engine, 16)
+    _evaluate_checked(engine, oracle, data, capfd, monkeypatch, Measure.PEARSON, oracle_lib.PEARSON,
+                      out=np.empty(N, dtype=np.float32), env={"CRF_HOST_HUGEPAGE": "0"}, what="Pearson, CRF_HOST_HUGEPAGE=0")
+
+
+@pytest.mark.parametrize("name,value,ranges", [("CRF_HOST_CHUNKS", "2", 2), ("CRF_HOST_CHUNKS", "16", 16),
+                                               ("CRF_HOST_SHARES", "32,32", 2)], ids=["chunks2", "chunks16", "shares32_32"])
+def test_ranged_host_range_counts(engine, oracle, capfd, monkeypatch, name, value, ranges):
+    """Another partition.  A context keeps its partition until the grid is set again, so the variable is set before
+    _data sets the grid (the poisoning evaluation builds the partition), and the grid is set once more afterwards."""
+    try:
+        with monkeypatch.context() as m:
+            m.setenv(name, value)
+            data = _data(engine, 16)
+            _evaluate_checked(engine, oracle, data, capfd, monkeypatch, Measure.PEARSON, oracle_lib.PEARSON, ranges=ranges,
+                              what=f"Pearson, {name}={value}")
+    finally:
+        _data(engine, 16)
+
+
+@pytest.mark.parametrize("threads", [1, 3])
+def test_ranged_host_copier_threads(engine, oracle, capfd, monkeypatch, threads):
+    """CRF_COPY_THREADS is read when a context builds its pool: a context of its own."""
+    data = _data(engine, 16)
+    monkeypatch.setenv("CRF_COPY_THREADS", str(threads))
+    own = ca.CorrField(0)
+    try:
+        own.set_grid(XS, YS, ZS, 16)
+        own.bind_members(data.members)
+        _evaluate_checked(own, oracle, data, capfd, monkeypatch, Measure.PEARSON, oracle_lib.PEARSON,
+                          copier_threads=threads, what=f"Pearson, CRF_COPY_THREADS={threads}")
+    finally:
+        own.close()
 
 
 def test_group_of_two_ranged_slabs(engine):
