@@ -541,42 +541,66 @@ int for_each_window(crf_context* c, float* out, Launch&& launch) {
     return CRF_OK;
 }
 
+// ---- two vectors per item: the symmetric field mode and pair requests -------------------------------------------------
+bool env_is_one(const char* name) {
+    const char* v = getenv(name);
+    return v && *v == '1';
+}
+
+// what both modes take from the context and the parameters; the caller adds its items, members_y, use_abs and out
+crf::TwoVectorJob two_vector_job(const crf_context* c, const crf_params* p) {
+    crf::TwoVectorJob job{};
+    job.members_x = job.members_y = c->view.members;
+    job.cs = c->cs, job.xs = c->xs, job.ys = c->ys;
+    job.num_voxels = c->view.num_voxels;
+    job.measure = p->measure, job.num_bins = p->num_bins, job.k = p->k;
+    job.min_x = p->min_ref, job.max_x = p->max_ref, job.min_y = p->min_query, job.max_y = p->max_query;
+    job.kraskov_c = kraskov_c_term(p->k > 0 ? p->k : 1, 1);
+    job.tables = c->grid.tables.get();
+    return job;
+}
+
+// One two-vector evaluation: takes the route (two_vector_route.h), reserves the workspace that route needs, calls the one
+// launcher.  *kernel: the name the route reports; *e: the launcher's status.  Returns non-zero only where the workspace
+// could not be had.
+int run_two_vector(crf_context* c, crf::TwoVectorJob job, bool force_counting, hipStream_t s, const char** kernel,
+                   hipError_t* e) {
+    using crf::TwoVectorKernel;
+    const bool requests = job.requests || job.num_items == 0;  // field mode has voxels; an empty list may come as null
+    const TwoVectorKernel route = crf::two_vector_route(requests, job.measure, job.cs, job.k, job.num_bins, force_counting,
+                                                        job.num_items < (size_t(1) << 32));
+    *kernel = crf::two_vector_kernel_name(route, requests, job.measure);
+    *e = hipSuccess;
+    if (job.num_items == 0) return CRF_OK;  // an empty request list
+    const size_t need = route == TwoVectorKernel::DirectSymmetric
+                            ? crf::direct_symmetric_workspace_bytes(job.cs, job.num_voxels, job.measure)
+                        : route == TwoVectorKernel::PairRequest ? crf::pair_workspace_bytes(job.cs, job.num_items)
+                                                                : 0;
+    if (int r = ensure_workspace(c, need)) return r;
+    job.workspace = c->grid.scratch[0].workspace.get();
+    const bool binned = job.measure == CRF_MI_BINNED || job.measure == CRF_BINNED_MI_CC;
+    switch (route) {
+        case TwoVectorKernel::Fill: *e = crf::launch_fill(job.out, job.num_items, 1.0f, s); break;
+        case TwoVectorKernel::PearsonRegister: *e = crf::launch_pearson_two_vector(job, s); break;
+        case TwoVectorKernel::KraskovDirect: *e = crf::launch_mi_kraskov_symmetric(job, s); break;
+        case TwoVectorKernel::Sorted: *e = binned ? crf::launch_sorted_binned(job, s) : crf::launch_sorted_rank(job, s); break;
+        case TwoVectorKernel::DirectSymmetric: *e = crf::launch_direct_symmetric(job, s); break;
+        case TwoVectorKernel::PairRequest: *e = crf::launch_pair_requests(job, s); break;
+    }
+    return CRF_OK;
+}
+
 // CRF_FLAG_SYMMETRIC: measure(primary members at v, secondary members at v) for every voxel v
 int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream_t s) {
     TimedLaunch launch(c);
     if (launch.e0) (void)hipEventRecord(launch.e0, s);
-    const char*& kernel = launch.info.kernel_name;
-    hipError_t e = hipErrorNotSupported;
-    if (p->measure == CRF_PEARSON) {
-        e = crf::launch_pearson_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, out, s);
-        kernel = "pearson_symmetric_kernel";
-    } else if (p->measure == CRF_MI_KRASKOV || p->measure == CRF_KMI_CC) {
-        e = crf::launch_mi_kraskov_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, p->k,
-                                             kraskov_c_term(p->k, 1), p->measure == CRF_KMI_CC, c->grid.tables.get(), out, s);
-        kernel = "kraskov_direct_kernel";
-    } else {  // Spearman, Kendall, the binned measures: sort-based where it applies, else the any-member-count kernel
-        const char* force_direct = getenv("CRF_SYMMETRIC_DIRECT");  // tuning / tests: the any-member-count kernel
-        if (!(force_direct && *force_direct == '1')) {
-            e = crf::launch_sorted_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, p->measure,
-                                             p->num_bins, p->min_ref, p->max_ref, p->min_query, p->max_query, c->grid.tables.get(),
-                                             out, s);
-            kernel = "sorted_symmetric_kernel";
-        }
-        if (e == hipErrorNotSupported) {
-            if (int r = ensure_workspace(c, crf::direct_symmetric_workspace_bytes(c->cs, c->view.num_voxels, p->measure))) return r;
-            e = crf::launch_direct_symmetric(c->view.members, c->view.secondary, c->cs, c->view.num_voxels, p->measure, p->num_bins,
-                                             p->min_ref, p->max_ref, p->min_query, p->max_query, c->grid.tables.get(),
-                                             c->grid.scratch[0].workspace.get(), out, s);
-            kernel = "direct_symmetric_kernel";
-        }
-    }
-    if (e == hipErrorNotSupported) {
-        if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, c->view.num_voxels))) return r;
-        const crf::PairArgs a{p->measure, p->num_bins, p->k, 0, kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
-        e = crf::launch_pair_requests(c->view.members, c->view.secondary, c->cs, c->xs, c->ys, c->view.num_voxels, nullptr,
-                                      c->view.num_voxels, a, c->grid.tables.get(), c->grid.scratch[0].workspace.get(), out, s);
-        kernel = "pair_request_kernel";
-    }
+    crf::TwoVectorJob job = two_vector_job(c, p);
+    job.members_y = c->view.secondary;
+    job.num_items = c->view.num_voxels;
+    job.out = out;
+    hipError_t e;
+    // CRF_SYMMETRIC_DIRECT=1 (tuning / tests): the any-member-count kernel instead of the sort-based ones
+    if (int r = run_two_vector(c, job, env_is_one("CRF_SYMMETRIC_DIRECT"), s, &launch.info.kernel_name, &e)) return r;
     if (launch.e0 && launch.e1) (void)hipEventRecord(launch.e1, s);
     return launch.finish(e);
 }
@@ -1347,41 +1371,24 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
     if (int r = bind_device(c)) return r;
     hipStream_t s = stream_of(c, stream);
     if (int r = ensure_wide(c, s)) return r;
-    if (int r = ensure_workspace(c, crf::pair_workspace_bytes(c->cs, num_requests))) return r;
+    crf::TwoVectorJob job = two_vector_job(c, p);
     // two-field request mode: the j side reads the secondary members (CRF_FLAG_QUERY_FROM_SECONDARY)
-    const float* const* members_j = c->view.members;
     if (p->flags & CRF_FLAG_QUERY_FROM_SECONDARY) {
         if (c->grid.secondary.ptrs.empty())
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_QUERY_FROM_SECONDARY needs secondary members (crf_upload_secondary_members)");
-        members_j = c->view.secondary;
+        job.members_y = c->view.secondary;
     }
-    const crf::PairArgs a{p->measure, p->num_bins, p->k, (p->flags & CRF_FLAG_ABSOLUTE_VALUE) ? 1 : 0,
-                          kraskov_c_term(p->k > 0 ? p->k : 1, 1)};
-    // Spearman / Kendall up to 128 members: the sort-based two-vector kernels (kernels_symmetric.hip) in request mode
-    hipError_t e = hipErrorNotSupported;
-    const char* force_generic = getenv("CRF_REQUESTS_GENERIC");  // tuning / tests: the counting kernel
-    if (!(force_generic && *force_generic == '1') && p->measure == CRF_PEARSON) {
-        e = crf::launch_pearson_requests(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
-                                         static_cast<const uint32_t*>(device_requests), num_requests, a.use_abs,
-                                         static_cast<float*>(device_out), s);
-        c->last_kernel = "pearson_request_kernel";
-    } else if (!(force_generic && *force_generic == '1') && (p->measure == CRF_MI_BINNED || p->measure == CRF_BINNED_MI_CC)) {
-        e = crf::launch_sorted_requests_binned(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
-                                               static_cast<const uint32_t*>(device_requests), num_requests, p->measure,
-                                               p->num_bins, a.use_abs, c->grid.tables.get(), static_cast<float*>(device_out), s);
-        c->last_kernel = "sorted_request_kernel";
-    } else if (!(force_generic && *force_generic == '1')) {
-        e = crf::launch_sorted_requests(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
-                                        static_cast<const uint32_t*>(device_requests), num_requests, p->measure,
-                                        a.use_abs, static_cast<float*>(device_out), s);
-        c->last_kernel = "sorted_request_kernel";
-    }
-    if (e == hipErrorNotSupported) {
-        e = crf::launch_pair_requests(c->view.members, members_j, c->cs, c->xs, c->ys, c->view.num_voxels,
-                                      static_cast<const uint32_t*>(device_requests), num_requests, a, c->grid.tables.get(),
-                                      c->grid.scratch[0].workspace.get(), static_cast<float*>(device_out), s);
-        c->last_kernel = "pair_request_kernel";
-    }
+    job.requests = static_cast<const uint32_t*>(device_requests);
+    job.num_items = num_requests;
+    job.use_abs = (p->flags & CRF_FLAG_ABSOLUTE_VALUE) ? 1 : 0;
+    job.out = static_cast<float*>(device_out);
+    // CRF_REQUESTS_GENERIC=1 (tuning / tests): the counting kernel for every measure.  A null list (legal only with no
+    // requests) launches nothing and reports that kernel too.
+    const bool force_counting = env_is_one("CRF_REQUESTS_GENERIC") || !job.requests;
+    const char* kernel = "";
+    hipError_t e;
+    if (int r = run_two_vector(c, job, force_counting, s, &kernel, &e)) return r;
+    c->last_kernel = kernel;
     return launch_status(c, e);
 }
 

@@ -6,14 +6,13 @@
 #include <cstdint>
 
 #include "../../include/corrfield.h"
+#include "two_vector_route.h"  // kMaxSortMembers, kMaxSymmetricRegisterMembers
 
 namespace crf {
 
 // Largest member count the register-resident kernels are instantiated for; above it the streaming
 // (re-reading) variants run.
 constexpr int kMaxRegisterMembers = 384;  // 257..384: VGPRs + AGPRs + a little scratch at one wave per SIMD
-// Largest member count supported at all by the sort-based estimators (LDS / register budgets).
-constexpr int kMaxSortMembers = 128;
 // Prepared reference-derived table: floats (see each kernels_*.hip for its layout).
 constexpr size_t kPrepBytes = 160 * 1024;  // (r02: room for the Kraskov x-distance table of 128 members, 133 KB)
 // Largest member count of the generic (any-cs) kernels: bounded by the preparation scratch (2*cs ints / doubles).
@@ -288,10 +287,6 @@ hipError_t launch_mi_kraskov_direct(const float* const* d_members, int cs, size_
                                     const KraskovArgs& a, const double* d_tables, float* d_prep, float* d_out,
                                     hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 
-hipError_t launch_mi_kraskov_symmetric(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                       size_t num_voxels, int k, double c_term, bool to_cc, const double* d_tables,
-                                       float* d_out, hipStream_t s);
-
 // ---- kernels_generic.hip: any member count (O(cs^2) counting algorithms, runtime loops) ------------------
 struct GenericArgs {
     int measure;  // crf_measure value
@@ -360,44 +355,36 @@ hipError_t launch_dkl_narrow(const void* const* d_narrow, int format, int cs, si
                              int k, double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s,
                              hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 
-// pair-request mode (kernels_generic.hip): requests = 8 uint32 each {xi,yi,zi,i,xj,yj,zj,j}; voxel i is read from
-// d_members_i, voxel j from d_members_j.  d_requests == nullptr: request r = voxel pair (r, r) (symmetric field mode).
-struct PairArgs {
-    int measure, num_bins, k, use_abs;  // binned MI normalises with the pair's own extrema (HEBChart)
-    double kraskov_c;  // psi(k) (pair requests are KSG-1), host-evaluated like KraskovArgs::c_term
+// ---- two vectors per item: the symmetric field mode and pair requests --------------------------------------------------
+// One evaluation of a measure between two member vectors per item.  Field mode (requests == nullptr): item v is voxel
+// pair (v, v), X = members_x[.][v] (the primary field), Y = members_y[.][v] (the secondary field).  Request mode: item r
+// is requests[8 r ..] = {xi,yi,zi,i,xj,yj,zj,j}, X = members_x at voxel i, Y = members_y at voxel j.  Which kernel serves
+// a job is two_vector_route's decision (two_vector_route.h); a launcher called outside the domain that table gives it
+// returns hipErrorInvalidValue.
+struct TwoVectorJob {
+    const float* const* members_x;
+    const float* const* members_y;
+    int cs, xs, ys;
+    size_t num_voxels;         // of every member volume
+    const uint32_t* requests;  // null: field mode
+    size_t num_items;          // voxels (field mode) or requests
+    int measure, num_bins;
+    float min_x, max_x, min_y, max_y;  // binned measures in field mode; requests normalise with the pair's own extrema
+    int k;
+    double kraskov_c;  // psi(k) (two-vector Kraskov is KSG-1), host-evaluated like KraskovArgs::c_term
+    int use_abs;       // request mode: |result|
+    const double* tables;
+    unsigned char* workspace;  // direct_symmetric_workspace_bytes / pair_workspace_bytes for the kernels that use one
+    float* out;
 };
 size_t pair_workspace_bytes(int cs, size_t num_requests);
-hipError_t launch_pair_requests(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs, int ys,
-                                size_t num_voxels, const uint32_t* d_requests, size_t num_requests, const PairArgs& a,
-                                const double* d_tables, unsigned char* d_workspace, float* d_out, hipStream_t s);
-// symmetric field mode, Spearman (measure 1) / Kendall (2) / binned MI (3, 5), any member count (kernels_generic.hip)
 size_t direct_symmetric_workspace_bytes(int cs, size_t num_voxels, int measure);
-// sort-based symmetric kernels (kernels_symmetric.hip): 2 <= cs <= kMaxSortMembers, measures 1, 2, 3, 5
-hipError_t launch_sorted_symmetric(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                   size_t num_voxels, int measure, int num_bins, float min_x, float max_x, float min_y,
-                                   float max_y, const double* d_tables, float* d_out, hipStream_t s);
-hipError_t launch_sorted_requests_binned(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs,
-                                         int ys, size_t num_voxels, const uint32_t* d_requests, size_t num_requests,
-                                         int measure, int num_bins, int use_abs, const double* d_tables, float* d_out,
-                                         hipStream_t s);
-hipError_t launch_pearson_requests(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs, int ys,
-                                   size_t num_voxels, const uint32_t* d_requests, size_t num_requests, int use_abs,
-                                   float* d_out, hipStream_t s);
-hipError_t launch_sorted_requests(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs, int ys,
-                                  size_t num_voxels, const uint32_t* d_requests, size_t num_requests, int measure,
-                                  int use_abs, float* d_out, hipStream_t s);
-hipError_t launch_sorted_symmetric_binned(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                          size_t num_voxels, int measure, int num_bins, float min_x, float max_x,
-                                          float min_y, float max_y, const double* d_tables, float* d_out, hipStream_t s);
-hipError_t launch_direct_symmetric(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                   size_t num_voxels, int measure, int num_bins, float min_x, float max_x, float min_y,
-                                   float max_y, const double* d_tables, unsigned char* d_workspace, float* d_out,
-                                   hipStream_t s);
-// symmetric field mode, Pearson, members resident in registers (kernels_pearson.hip); hipErrorNotSupported above
-// kMaxSymmetricRegisterMembers (the caller then uses launch_pair_requests)
-constexpr int kMaxSymmetricRegisterMembers = 128;
-hipError_t launch_pearson_symmetric(const float* const* d_members_ref, const float* const* d_members_query, int cs,
-                                    size_t num_voxels, float* d_out, hipStream_t s);
+hipError_t launch_pearson_two_vector(const TwoVectorJob& job, hipStream_t s);    // kernels_pearson.hip
+hipError_t launch_sorted_rank(const TwoVectorJob& job, hipStream_t s);           // kernels_symmetric.hip: Spearman, Kendall
+hipError_t launch_sorted_binned(const TwoVectorJob& job, hipStream_t s);         // kernels_symmetric_binned.hip
+hipError_t launch_mi_kraskov_symmetric(const TwoVectorJob& job, hipStream_t s);  // kernels_kraskov.hip, field mode
+hipError_t launch_direct_symmetric(const TwoVectorJob& job, hipStream_t s);      // kernels_generic.hip, field mode
+hipError_t launch_pair_requests(const TwoVectorJob& job, hipStream_t s);         // kernels_generic.hip
 // preparation launchers shared with the generic path (kernels_rank.hip / kernels_binned.hip / kernels_kraskov.hip); n_pad = table stride
 void launch_spearman_prep(const RefSource& ref, const float* const* d_members, int cs, float* d_prep, hipStream_t s);
 void launch_kendall_prep(const RefSource& ref, const float* const* d_members, int cs, int n_pad, int* d_prep,

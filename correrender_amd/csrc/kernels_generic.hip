@@ -599,19 +599,18 @@ __global__ __launch_bounds__(64) void direct_symmetric_kernel(const float* const
     }
 }
 
-hipError_t launch_direct_symmetric(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                   size_t num_voxels, int measure, int num_bins, float min_x, float max_x, float min_y,
-                                   float max_y, const double* d_tables, unsigned char* d_workspace, float* d_out,
-                                   hipStream_t s) {
-    if (measure != 1 && measure != 2 && measure != 3 && measure != 5) return hipErrorNotSupported;
-    if (measure != 2 && !d_workspace) return hipErrorInvalidValue;
-    const unsigned blocks = unsigned(persistent_blocks(num_voxels, kDirectBlocks));
-    const SymmetricBinnedArgs ba{num_bins, min_x, max_x, min_y, max_y, measure == 5};
-    uint16_t* ws = reinterpret_cast<uint16_t*>(d_workspace);
-    const double* tableT = d_tables + (cs + 1);
-#define CRF_LAUNCH_SYMMETRIC(M)                                                                                       \
-    hipLaunchKernelGGL((direct_symmetric_kernel<M>), dim3(blocks), dim3(64), 0, s, d_members_x, d_members_y, d_out,   \
-                       num_voxels, cs, ws, ba, tableT)
+// field mode only; which evaluations arrive here: two_vector_route.h
+hipError_t launch_direct_symmetric(const TwoVectorJob& job, hipStream_t s) {
+    const int measure = job.measure;
+    if (job.requests || (measure != 1 && measure != 2 && measure != 3 && measure != 5)) return hipErrorInvalidValue;
+    if (measure != 2 && !job.workspace) return hipErrorInvalidValue;
+    const unsigned blocks = unsigned(persistent_blocks(job.num_voxels, kDirectBlocks));
+    const SymmetricBinnedArgs ba{job.num_bins, job.min_x, job.max_x, job.min_y, job.max_y, measure == 5};
+    uint16_t* ws = reinterpret_cast<uint16_t*>(job.workspace);
+    const double* tableT = job.tables + (job.cs + 1);
+#define CRF_LAUNCH_SYMMETRIC(M)                                                                                        \
+    hipLaunchKernelGGL((direct_symmetric_kernel<M>), dim3(blocks), dim3(64), 0, s, job.members_x, job.members_y, job.out, \
+                       job.num_voxels, job.cs, ws, ba, tableT)
     switch (measure) {
         case 1: CRF_LAUNCH_SYMMETRIC(1); break;
         case 2: CRF_LAUNCH_SYMMETRIC(2); break;
@@ -726,8 +725,12 @@ __device__ float kraskov_pair(const float* x, const float* y, const double* __re
 
 // members_i / members_j: the member sets the first / second voxel of a request is read from (the same table for the
 // request mode; primary / secondary field for the symmetric field mode).  requests == nullptr: request r is the
-// voxel pair (r, r) -- SEPARATE_SYMMETRIC, CorrelationMain.glsl:10-15; only Pearson above 128 members and Kraskov
-// with min(k, cs - 1) > 64 arrive that way.  Binned MI normalises with the pair's own extrema (HEBChart).
+// voxel pair (r, r) -- SEPARATE_SYMMETRIC, CorrelationMain.glsl:10-15; which evaluations arrive in either mode:
+// two_vector_route.h.  Binned MI normalises with the pair's own extrema (HEBChart).
+struct PairArgs {
+    int measure, num_bins, k, use_abs;
+    double kraskov_c;  // psi(k) (pair requests are KSG-1), host-evaluated like KraskovArgs::c_term
+};
 __global__ __launch_bounds__(64) void pair_request_kernel(const float* const* __restrict__ members_i,
                                                           const float* const* __restrict__ members_j,
                                                           const uint32_t* __restrict__ requests,
@@ -801,16 +804,14 @@ __global__ __launch_bounds__(64) void pair_request_kernel(const float* const* __
     }
 }
 
-hipError_t launch_pair_requests(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs, int ys,
-                                size_t num_voxels, const uint32_t* d_requests, size_t num_requests, const PairArgs& a,
-                                const double* d_tables, unsigned char* d_workspace, float* d_out, hipStream_t s) {
-    if (num_requests == 0) return hipSuccess;
-    const unsigned blocks = unsigned(persistent_blocks(num_requests, kGenericBlocks));
-    const bool use_lds = pair_tile_bytes(cs) <= kLdsTileLimit;
-    if (!use_lds && !d_workspace) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pair_request_kernel, dim3(blocks), dim3(64), use_lds ? pair_tile_bytes(cs) : 0, s, d_members_i,
-                       d_members_j, d_requests, d_tables, d_out, num_requests, num_voxels, xs, ys, cs, a,
-                       use_lds ? nullptr : d_workspace);
+hipError_t launch_pair_requests(const TwoVectorJob& job, hipStream_t s) {
+    const unsigned blocks = unsigned(persistent_blocks(job.num_items, kGenericBlocks));
+    const bool use_lds = pair_tile_bytes(job.cs) <= kLdsTileLimit;
+    if (job.num_items == 0 || (!use_lds && !job.workspace)) return hipErrorInvalidValue;
+    const PairArgs a{job.measure, job.num_bins, job.k, job.use_abs, job.kraskov_c};
+    hipLaunchKernelGGL(pair_request_kernel, dim3(blocks), dim3(64), use_lds ? pair_tile_bytes(job.cs) : 0, s, job.members_x,
+                       job.members_y, job.requests, job.tables, job.out, job.num_items, job.num_voxels, job.xs, job.ys, job.cs,
+                       a, use_lds ? nullptr : job.workspace);
     return hipGetLastError();
 }
 

@@ -930,16 +930,15 @@ hipError_t launch_mi_kraskov_direct(const float* const* d_members, int cs, size_
     return launch_field(plan, d_members, cs, num_voxels, ref, a, d_tables, d_prep, d_out, s, ev_begin, ev_end, info);
 }
 
-// symmetric field mode: X = d_members_x (reference field), Y = d_members_y (query field); KSG-1
-hipError_t launch_mi_kraskov_symmetric(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                       size_t num_voxels, int k, double c_term, bool to_cc, const double* d_tables,
-                                       float* d_out, hipStream_t s) {
-    if (cs == 1) return launch_fill(d_out, num_voxels, 1.0f, s);
+// symmetric field mode: X = job.members_x (reference field), Y = job.members_y (query field); KSG-1, 2 <= cs, where
+// kraskov_symmetric_plan accepts (cs, k) -- two_vector_route.h sends everything else to pair_request_kernel
+hipError_t launch_mi_kraskov_symmetric(const TwoVectorJob& job, hipStream_t s) {
     KraskovPlan plan;
-    if (!kraskov_symmetric_plan(cs, k, &plan)) return hipErrorNotSupported;
-    const KraskovTables t = kraskov_tables(d_tables, cs);
-    launch_direct(direct_plain_kernel<true>(plan), plan, num_voxels, cs, s, d_members_y, d_members_x, t.noise_ref, t.psi,
-                  t.noise_query, d_out, num_voxels, cs, k, 1, int(to_cc), c_term);
+    if (job.requests || job.cs < 2 || !kraskov_symmetric_plan(job.cs, job.k, &plan)) return hipErrorInvalidValue;
+    const KraskovTables t = kraskov_tables(job.tables, job.cs);
+    launch_direct(direct_plain_kernel<true>(plan), plan, job.num_voxels, job.cs, s, job.members_y, job.members_x, t.noise_ref,
+                  t.psi, t.noise_query, job.out, job.num_voxels, job.cs, job.k, 1, int(job.measure == CRF_KMI_CC),
+                  job.kraskov_c);
     return hipGetLastError();
 }
 

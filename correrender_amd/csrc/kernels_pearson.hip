@@ -18,6 +18,7 @@
 // No LDS, no MFMA: ~4 flop/byte, HBM-read bound.
 #include "crf_device.h"
 #include "crf_internal.h"
+#include "crf_two_vector_device.h"
 
 namespace crf {
 
@@ -892,6 +893,7 @@ __global__ __launch_bounds__(64) void pearson_narrow_tail_kernel(const void* con
 // REQ: pair-request mode (crf_compute_requests): item r works on request r = {xi, yi, zi, i, xj, yj, zj, j}
 // (HEBChart.hpp:166-168), X = the members at voxel i, Y = the members at voxel j; default cache policy (requests
 // revisit voxels); `requests`, `xs`, `ys`, `use_abs` are unused in field mode, where num_items = num_voxels.
+// Which evaluations arrive here: two_vector_route.h.
 template <int CS_PAD, bool EXACT, int MIN_WAVES, bool REQ = false>
 __global__ __launch_bounds__(256, MIN_WAVES) void pearson_symmetric_kernel(const float* const* __restrict__ members_x,
                                                                            const float* const* __restrict__ members_y,
@@ -900,23 +902,15 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_symmetric_kernel(const
                                                                            const uint32_t* __restrict__ requests,
                                                                            uint32_t num_items, int xs, int ys,
                                                                            int use_abs) {
-    constexpr int kFirstGuarded = EXACT ? CS_PAD : CS_PAD - 16;
-    const auto is_member = [cs](int e) { return e < kFirstGuarded || e < cs; };
+    const auto is_member = [cs](int e) { return CRF_SLOT_IS_MEMBER(CS_PAD, EXACT, e, cs); };
     const uint32_t v0 = blockIdx.x * 256 + threadIdx.x;
-    uint32_t offset_x = v0 * 4u, offset_y = v0 * 4u;
-    if constexpr (REQ) {
-        offset_x = offset_y = kOutOfRangeOffset;  // items past the end read 0 and store nothing
-        if (v0 < num_items) {
-            const uint32_t* q = requests + size_t(v0) * 8;
-            offset_x = ((q[2] * uint32_t(ys) + q[1]) * uint32_t(xs) + q[0]) * 4u;  // IDXS
-            offset_y = ((q[6] * uint32_t(ys) + q[5]) * uint32_t(xs) + q[4]) * 4u;
-        }
-    }
+    uint32_t offset_x, offset_y;
+    lane_offsets<REQ>(RequestArgs{requests, xs, ys, use_abs}, v0, num_items, offset_x, offset_y);
     const uint32_t bytes = num_voxels * 4u;
     float x[CS_PAD], y[CS_PAD];
 #pragma unroll
     for (int e = 0; e < CS_PAD; e++) {
-        const int slot = (e < kFirstGuarded || e < cs) ? e : cs - 1;
+        const int slot = is_member(e) ? e : cs - 1;
         const uint32_t off_x = is_member(e) ? offset_x : kOutOfRangeOffset;
         const uint32_t off_y = is_member(e) ? offset_y : kOutOfRangeOffset;
         x[e] = REQ ? load_member_cached(members_x[slot], bytes, off_x) : load_member_nt(members_x[slot], bytes, off_x);
@@ -1180,70 +1174,34 @@ hipError_t launch_fill(float* d_out, size_t n, float value, hipStream_t s) {
 
 namespace {
 template <int CS_PAD>
-void launch_symmetric(const float* const* mx, const float* const* my, int cs, size_t num_voxels, float* d_out,
-                      hipStream_t s) {
+void launch_two_vector(const TwoVectorJob& j, hipStream_t s) {
     // 2 * CS_PAD values per lane.  Two waves under a 256-register cap pay off at 96 (90 members: 2.55 -> 2.04 ms) but
-    // not with the 72-670 B of scratch of the 112 / 128 instantiations (128 members: 3.92 -> 5.09 ms)
-    constexpr int kMinWaves = CS_PAD <= 32 ? 4 : (CS_PAD <= 64 || CS_PAD == 96 ? 2 : 1);
-    const unsigned blocks = unsigned((num_voxels + 255) / 256);
-    if (cs == CS_PAD)
-        hipLaunchKernelGGL((pearson_symmetric_kernel<CS_PAD, true, kMinWaves>), dim3(blocks), dim3(256), 0, s, mx, my,
-                           d_out, uint32_t(num_voxels), cs, nullptr, uint32_t(num_voxels), 0, 0, 0);
-    else
-        hipLaunchKernelGGL((pearson_symmetric_kernel<CS_PAD, false, kMinWaves>), dim3(blocks), dim3(256), 0, s, mx, my,
-                           d_out, uint32_t(num_voxels), cs, nullptr, uint32_t(num_voxels), 0, 0, 0);
+    // not with the 72-670 B of scratch of the 112 / 128 instantiations (128 members: 3.92 -> 5.09 ms); request mode
+    // (cached loads, the guarded instantiations only) takes two waves at 80 as well
+    constexpr int kFieldWaves = CS_PAD <= 32 ? 4 : (CS_PAD <= 64 || CS_PAD == 96 ? 2 : 1);
+    constexpr int kRequestWaves = CS_PAD <= 32 ? 4 : (CS_PAD <= 96 ? 2 : 1);
+    const auto kernel = j.requests       ? pearson_symmetric_kernel<CS_PAD, false, kRequestWaves, true>
+                        : j.cs == CS_PAD ? pearson_symmetric_kernel<CS_PAD, true, kFieldWaves>
+                                         : pearson_symmetric_kernel<CS_PAD, false, kFieldWaves>;
+    hipLaunchKernelGGL(kernel, dim3(unsigned((j.num_items + 255) / 256)), dim3(256), 0, s, j.members_x, j.members_y, j.out,
+                       uint32_t(j.num_voxels), j.cs, j.requests, uint32_t(j.num_items), j.xs, j.ys, j.use_abs);
 }
 }  // namespace
 
-namespace {
-template <int CS_PAD>
-void launch_symmetric_requests(const float* const* mi, const float* const* mj, int cs, size_t num_voxels,
-                               const uint32_t* d_requests, size_t num_requests, int xs, int ys, int use_abs, float* d_out,
-                               hipStream_t s) {
-    constexpr int kMinWaves = CS_PAD <= 32 ? 4 : (CS_PAD <= 96 ? 2 : 1);
-    hipLaunchKernelGGL((pearson_symmetric_kernel<CS_PAD, false, kMinWaves, true>), dim3(unsigned((num_requests + 255) / 256)),
-                       dim3(256), 0, s, mi, mj, d_out, uint32_t(num_voxels), cs, d_requests, uint32_t(num_requests), xs, ys,
-                       use_abs);
-}
-}  // namespace
-
-// Pearson pair requests through the two-vector register kernel: 2 <= cs <= kMaxSymmetricRegisterMembers, fewer than
-// 2^32 requests; hipErrorNotSupported otherwise (-> pair_request_kernel)
-hipError_t launch_pearson_requests(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs, int ys,
-                                   size_t num_voxels, const uint32_t* d_requests, size_t num_requests, int use_abs,
-                                   float* d_out, hipStream_t s) {
-    if (cs < 2 || cs > kMaxSymmetricRegisterMembers || !d_requests || num_requests >= (size_t(1) << 32))
-        return hipErrorNotSupported;
-    if (num_requests == 0) return hipSuccess;
-#define CRF_REQ_CASE(I, N) \
-    case I: launch_symmetric_requests<N>(d_members_i, d_members_j, cs, num_voxels, d_requests, num_requests, xs, ys, use_abs, d_out, s); break
-    switch ((cs + 15) / 16) {
-        CRF_REQ_CASE(1, 16);
-        CRF_REQ_CASE(2, 32);
-        CRF_REQ_CASE(3, 48);
-        CRF_REQ_CASE(4, 64);
-        CRF_REQ_CASE(5, 80);
-        CRF_REQ_CASE(6, 96);
-        CRF_REQ_CASE(7, 112);
-        default: launch_symmetric_requests<128>(d_members_i, d_members_j, cs, num_voxels, d_requests, num_requests, xs, ys, use_abs, d_out, s); break;
-    }
-#undef CRF_REQ_CASE
-    return hipGetLastError();
-}
-
-hipError_t launch_pearson_symmetric(const float* const* d_members_ref, const float* const* d_members_query, int cs,
-                                    size_t num_voxels, float* d_out, hipStream_t s) {
-    if (cs == 1) return launch_fill(d_out, num_voxels, 1.0f, s);
-    if (cs > kMaxSymmetricRegisterMembers) return hipErrorNotSupported;
-    switch ((cs + 15) / 16) {
-        case 1: launch_symmetric<16>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
-        case 2: launch_symmetric<32>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
-        case 3: launch_symmetric<48>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
-        case 4: launch_symmetric<64>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
-        case 5: launch_symmetric<80>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
-        case 6: launch_symmetric<96>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
-        case 7: launch_symmetric<112>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
-        default: launch_symmetric<128>(d_members_ref, d_members_query, cs, num_voxels, d_out, s); break;
+// Pearson between two vectors per item, both in registers: 2 <= cs <= kMaxSymmetricRegisterMembers, fewer than 2^32 items
+hipError_t launch_pearson_two_vector(const TwoVectorJob& job, hipStream_t s) {
+    if (job.measure != CRF_PEARSON || job.cs < 2 || job.cs > kMaxSymmetricRegisterMembers ||
+        job.num_items >= (size_t(1) << 32))
+        return hipErrorInvalidValue;
+    switch ((job.cs + 15) / 16) {
+        case 1: launch_two_vector<16>(job, s); break;
+        case 2: launch_two_vector<32>(job, s); break;
+        case 3: launch_two_vector<48>(job, s); break;
+        case 4: launch_two_vector<64>(job, s); break;
+        case 5: launch_two_vector<80>(job, s); break;
+        case 6: launch_two_vector<96>(job, s); break;
+        case 7: launch_two_vector<112>(job, s); break;
+        default: launch_two_vector<128>(job, s); break;
     }
     return hipGetLastError();
 }

@@ -4,8 +4,9 @@
 //
 // Both vectors of a voxel depend on the voxel, so nothing can be prepared once per evaluation: the one-reference
 // kernels' preparation (ranks / sort order / bins of the reference vector) happens per voxel here, with the same
-// register-resident networks (crf_device.h).  The any-member-count fallback (direct_symmetric_kernel,
-// kernels_generic.hip) counts in O(cs^2) per voxel; at 256^3 x 64 it needs 25 / 21 / 37 ms where these need a few.
+// register-resident networks (crf_device.h).  The counting kernel for any member count (direct_symmetric_kernel,
+// kernels_generic.hip) is O(cs^2) per voxel; at 256^3 x 64 it needs 25 / 21 / 37 ms where these need a few.
+// The same kernels serve pair requests (REQ).  Which evaluations arrive here: two_vector_route.h.
 //   Spearman: two sorts -> doubled fractional ranks of X and of Y in two 16-bit LDS columns -> computePearson2<float>
 //             on the two rank vectors in member order (Correlation.cpp:141-174).
 //   Kendall : sort X as (key, member) -> each member's position in the X order and the last position of its X-tie group
@@ -17,8 +18,7 @@
 // One lane per voxel, one wave per block; pads (slots >= cs) load at kOutOfRangeOffset and sort last.
 #include <cstdlib>
 
-#include "crf_device.h"
-#include "crf_internal.h"
+#include "crf_two_vector_device.h"
 
 namespace crf {
 
@@ -26,21 +26,14 @@ namespace {
 
 constexpr uint32_t kPadKey = 0xFFFFFFFFu;  // sorts after every real value (orderable_key(+inf) = 0xFF800000)
 
-// the first N - 16 slots are members whatever cs is: launch_* picks the smallest N (a multiple of 16) that holds cs
-template <int N>
-constexpr int sure_slots() {
-    return N - 16;
-}
-
 // CACHED: default cache policy instead of non-temporal loads (pair requests revisit voxels)
 template <int N, bool EXACT, bool CACHED = false>
 __device__ __forceinline__ void load_composites(composite_t (&a)[N], const float* const* __restrict__ members, int cs,
                                                 uint32_t bytes, uint32_t byte_offset) {
-    constexpr int SURE = sure_slots<N>();
     float y[N];
 #pragma unroll
     for (int e = 0; e < N; e++) {
-        const bool real = EXACT || e < SURE || e < cs;
+        const bool real = CRF_SLOT_IS_MEMBER(N, EXACT, e, cs);
         const uint32_t off = real ? byte_offset : kOutOfRangeOffset;
         y[e] = CACHED ? load_member_cached(members[real ? e : cs - 1], bytes, off)
                       : load_member_nt(members[real ? e : cs - 1], bytes, off);
@@ -48,7 +41,7 @@ __device__ __forceinline__ void load_composites(composite_t (&a)[N], const float
 #pragma unroll
     for (int e = 0; e < N; e++) {
         const float yc = y[e] + 0.0f;  // -0.0 -> +0.0: key equality is float equality
-        a[e] = make_composite((EXACT || e < SURE || e < cs) ? orderable_key(yc) : kPadKey, uint32_t(e));
+        a[e] = make_composite(CRF_SLOT_IS_MEMBER(N, EXACT, e, cs) ? orderable_key(yc) : kPadKey, uint32_t(e));
     }
 }
 
@@ -81,17 +74,16 @@ __device__ __forceinline__ bool rank_side(const float* const* __restrict__ membe
     // 2 * rank = 2 * position + 2 and the two tie-run scans (~8 vector instructions per element) are skipped.  Pads are
     // left out of the test (they tie with each other) and their rank slots are never read as ranks.
     {
-        constexpr int SURE = sure_slots<N>();
         uint32_t tie_min = 0xFFFFFFFFu;  // min over neighbouring members of (key ^ previous key): 0 iff a tie
 #pragma unroll
         for (int p = 1; p < N; p++) {
             const uint32_t x = composite_key(a[p]) ^ composite_key(a[p - 1]);
-            tie_min = min(tie_min, (EXACT || p < SURE || p < cs) ? x : 0xFFFFFFFFu);
+            tie_min = min(tie_min, CRF_SLOT_IS_MEMBER(N, EXACT, p, cs) ? x : 0xFFFFFFFFu);
         }
         if (!__any(tie_min == 0u)) {
 #pragma unroll
             for (int p = 0; p < N; p++)
-                if (EXACT || p < SURE || p < cs) rank2[(composite_low(a[p]) & 0xFFu) * 64] = uint16_t(2 * p + 2);
+                if (CRF_SLOT_IS_MEMBER(N, EXACT, p, cs)) rank2[(composite_low(a[p]) & 0xFFu) * 64] = uint16_t(2 * p + 2);
             return is_nan;
         }
     }
@@ -118,28 +110,6 @@ __device__ __forceinline__ bool rank_side(const float* const* __restrict__ membe
     return is_nan;
 }
 
-// What a lane works on.  Field mode (REQ = false): voxel `item` of both fields.  Request mode: pair request `item`
-// (layout {xi, yi, zi, i, xj, yj, zj, j}, HEBChart.hpp:166-168): X = the members at voxel i, Y = the members at voxel j.
-struct RequestArgs {
-    const uint32_t* requests;
-    int xs, ys;
-    int use_abs;
-};
-template <bool REQ>
-__device__ __forceinline__ void lane_offsets(const RequestArgs& ra, size_t item, size_t num_items, uint32_t& offset_x,
-                                             uint32_t& offset_y) {
-    if constexpr (REQ) {
-        offset_x = offset_y = kOutOfRangeOffset;  // lanes past the end read 0 and store nothing
-        if (item < num_items) {
-            const uint32_t* q = ra.requests + item * 8;
-            offset_x = ((q[2] * uint32_t(ra.ys) + q[1]) * uint32_t(ra.xs) + q[0]) * 4u;  // IDXS
-            offset_y = ((q[6] * uint32_t(ra.ys) + q[5]) * uint32_t(ra.xs) + q[4]) * 4u;
-        }
-    } else {
-        offset_x = offset_y = uint32_t(item) * 4u;
-    }
-}
-
 }  // namespace
 
 template <int N, bool EXACT, int MIN_WAVES, bool REQ = false>
@@ -148,7 +118,6 @@ __global__ __launch_bounds__(64, MIN_WAVES) void spearman_symmetric_kernel(const
                                                                            float* __restrict__ out, size_t num_voxels,
                                                                            int cs, size_t num_items, RequestArgs ra) {
     __shared__ uint16_t rank2[2 * N * 64];
-    constexpr int SURE = sure_slots<N>();
     const int lane = threadIdx.x;
     const size_t v = size_t(blockIdx.x) * 64 + lane;
     const uint32_t bytes = uint32_t(num_voxels) * 4u;  // lanes past the end read 0
@@ -168,7 +137,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void spearman_symmetric_kernel(const
     float rx[N], ry[N];
 #pragma unroll
     for (int e = 0; e < N; e++) {
-        const bool member = EXACT || e < SURE || e < cs;
+        const bool member = CRF_SLOT_IS_MEMBER(N, EXACT, e, cs);
         rx[e] = member ? 0.5f * float(rank2[e * 64 + lane]) : 0.0f;
         ry[e] = member ? 0.5f * float(rank2[(N + e) * 64 + lane]) : 0.0f;
     }
@@ -184,7 +153,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void spearman_symmetric_kernel(const
     float varX = 0.0f, varY = 0.0f;
 #pragma unroll
     for (int e = 0; e < N; e++) {
-        const bool member = EXACT || e < SURE || e < cs;
+        const bool member = CRF_SLOT_IS_MEMBER(N, EXACT, e, cs);
         rx[e] = member ? rx[e] - meanX : 0.0f;
         ry[e] = member ? ry[e] - meanY : 0.0f;
         varX += invNm1 * rx[e] * rx[e];
@@ -199,7 +168,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void spearman_symmetric_kernel(const
     } else {
 #pragma unroll
         for (int e = 0; e < N; e++) {
-            const bool member = EXACT || e < SURE || e < cs;
+            const bool member = CRF_SLOT_IS_MEMBER(N, EXACT, e, cs);
             r += member ? invNm1 * (rx[e] / sdX) * (ry[e] / sdY) : 0.0f;
         }
     }
@@ -217,7 +186,6 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_symmetric_kernel(const 
     // N > 64: the Y order as a second column, [position][lane]: member | (same Y as the previous position) << 8
     constexpr bool kRolledWalk = N > 64;
     __shared__ uint16_t yseq[kRolledWalk ? N * 64 : 64];
-    constexpr int SURE = sure_slots<N>();
     const int lane = threadIdx.x;
     const size_t v = size_t(blockIdx.x) * 64 + lane;
     const uint32_t bytes = uint32_t(num_voxels) * 4u;
@@ -237,7 +205,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_symmetric_kernel(const 
 #pragma unroll
         for (int p = 1; p < N; p++) {
             const bool same = composite_key(a[p]) == composite_key(a[p - 1]);
-            run = ((EXACT || p < SURE || p < cs) && same) ? run + 1 : 0;
+            run = (CRF_SLOT_IS_MEMBER(N, EXACT, p, cs) && same) ? run + 1 : 0;
             n1 += run;
         }
         uint32_t run_end = 0;
@@ -286,7 +254,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_symmetric_kernel(const 
             const uint32_t key = composite_key(b[p]);
             const bool same = p > 0 && key == prev_key;
             if (p > 0) {
-                run = ((EXACT || p < SURE || p < cs) && same) ? run + 1 : 0;  // ties in Y: t(t-1)/2 per run
+                run = (CRF_SLOT_IS_MEMBER(N, EXACT, p, cs) && same) ? run + 1 : 0;  // ties in Y: t(t-1)/2 per run
                 n2 += run;
             }
             prev_key = key;
@@ -323,7 +291,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_symmetric_kernel(const 
         const uint32_t key = composite_key(b[p]);
         const bool same = p > 0 && key == prev_key;
         if (p > 0) {
-            run = ((EXACT || p < SURE || p < cs) && same) ? run + 1 : 0;  // ties in Y: t(t-1)/2 per run
+            run = (CRF_SLOT_IS_MEMBER(N, EXACT, p, cs) && same) ? run + 1 : 0;  // ties in Y: t(t-1)/2 per run
             n2 += run;
         }
         prev_key = key;
@@ -375,110 +343,59 @@ __global__ __launch_bounds__(64, MIN_WAVES) void kendall_symmetric_kernel(const 
 
 namespace {
 
-template <template <int, bool, int> class Launcher, int N, int WAVES, class... Args>
-void launch_exact_or_guarded(int cs, Args... args) {
-    if (cs == N)
-        Launcher<N, true, WAVES>::launch(args...);
+template <int MEASURE, int N, bool EXACT, int WAVES, bool REQ>
+constexpr auto rank_kernel() {
+    if constexpr (MEASURE == CRF_SPEARMAN)
+        return &spearman_symmetric_kernel<N, EXACT, WAVES, REQ>;
     else
-        Launcher<N, false, WAVES>::launch(args...);
+        return &kendall_symmetric_kernel<N, EXACT, WAVES, REQ>;
 }
 
-template <int N, bool EXACT, int WAVES>
-struct SpearmanLauncher {
-    static void launch(const float* const* mx, const float* const* my, float* out, size_t num_voxels, int cs,
-                       size_t num_items, RequestArgs ra, hipStream_t s) {
-        const dim3 grid(unsigned((num_items + 63) / 64));
-        if (ra.requests) {
-            if constexpr (!EXACT)  // request mode: the guarded instantiations only
-                hipLaunchKernelGGL((spearman_symmetric_kernel<N, false, WAVES, true>), grid, dim3(64), 0, s, mx, my, out,
-                                   num_voxels, cs, num_items, ra);
-        } else {
-            hipLaunchKernelGGL((spearman_symmetric_kernel<N, EXACT, WAVES, false>), grid, dim3(64), 0, s, mx, my, out,
-                               num_voxels, cs, num_items, ra);
+template <int MEASURE>
+struct RankMeasure {
+    template <int N, bool EXACT, int WAVES>
+    struct Launcher {
+        static void launch(const TwoVectorJob& j, hipStream_t s) {
+            const dim3 grid(unsigned((j.num_items + 63) / 64));
+            if (j.requests) {
+                if constexpr (!EXACT)  // request mode: the guarded instantiations only
+                    hipLaunchKernelGGL((rank_kernel<MEASURE, N, false, WAVES, true>()), grid, dim3(64), 0, s, j.members_x,
+                                       j.members_y, j.out, j.num_voxels, j.cs, j.num_items, request_args(j));
+            } else {
+                hipLaunchKernelGGL((rank_kernel<MEASURE, N, EXACT, WAVES, false>()), grid, dim3(64), 0, s, j.members_x,
+                                   j.members_y, j.out, j.num_voxels, j.cs, j.num_items, request_args(j));
+            }
         }
-    }
-};
-template <int N, bool EXACT, int WAVES>
-struct KendallLauncher {
-    static void launch(const float* const* mx, const float* const* my, float* out, size_t num_voxels, int cs,
-                       size_t num_items, RequestArgs ra, hipStream_t s) {
-        const dim3 grid(unsigned((num_items + 63) / 64));
-        if (ra.requests) {
-            if constexpr (!EXACT)
-                hipLaunchKernelGGL((kendall_symmetric_kernel<N, false, WAVES, true>), grid, dim3(64), 0, s, mx, my, out,
-                                   num_voxels, cs, num_items, ra);
-        } else {
-            hipLaunchKernelGGL((kendall_symmetric_kernel<N, EXACT, WAVES, false>), grid, dim3(64), 0, s, mx, my, out,
-                               num_voxels, cs, num_items, ra);
-        }
-    }
-};
+    };
 
-}  // namespace
-
-namespace {
-
-// exact = may the unguarded instantiation be used (field mode with cs a multiple of 16)
-hipError_t launch_sorted_rank(const float* const* d_members_x, const float* const* d_members_y, int cs, size_t num_voxels,
-                              int measure, float* d_out, size_t num_items, const RequestArgs& ra, hipStream_t s) {
-    const int n = (cs + 15) / 16 * 16;
-    const int cs_sel = ra.requests ? -1 : cs;  // request mode: never the unguarded instantiation
-#define CRF_SYM_CASE(L, N, W) \
-    case N: launch_exact_or_guarded<L, N, W>(cs_sel, d_members_x, d_members_y, d_out, num_voxels, cs, num_items, ra, s); break
-    if (measure == 1) {
-        switch (n) {
-            CRF_SYM_CASE(SpearmanLauncher, 16, 4);
-            CRF_SYM_CASE(SpearmanLauncher, 32, 3);
-            CRF_SYM_CASE(SpearmanLauncher, 48, 2);
-            CRF_SYM_CASE(SpearmanLauncher, 64, 2);
-            CRF_SYM_CASE(SpearmanLauncher, 80, 2);
-            CRF_SYM_CASE(SpearmanLauncher, 96, 1);
-            CRF_SYM_CASE(SpearmanLauncher, 112, 1);
-            CRF_SYM_CASE(SpearmanLauncher, 128, 1);
-            default: return hipErrorNotSupported;
+    static void launch(const TwoVectorJob& j, hipStream_t s) {
+#define CRF_SYM_CASE(N, W) \
+    case N: launch_exact_or_guarded<Launcher, N, W>(j, s); break
+        switch ((j.cs + 15) / 16 * 16) {
+            CRF_SYM_CASE(16, 4);
+            CRF_SYM_CASE(32, 3);
+            CRF_SYM_CASE(48, 2);
+            CRF_SYM_CASE(64, 2);
+            CRF_SYM_CASE(80, (MEASURE == CRF_SPEARMAN ? 2 : 1));
+            CRF_SYM_CASE(96, 1);
+            CRF_SYM_CASE(112, 1);
+            default: launch_exact_or_guarded<Launcher, 128, 1>(j, s); break;
         }
-    } else {
-        switch (n) {
-            CRF_SYM_CASE(KendallLauncher, 16, 4);
-            CRF_SYM_CASE(KendallLauncher, 32, 3);
-            CRF_SYM_CASE(KendallLauncher, 48, 2);
-            CRF_SYM_CASE(KendallLauncher, 64, 2);
-            CRF_SYM_CASE(KendallLauncher, 80, 1);
-            CRF_SYM_CASE(KendallLauncher, 96, 1);
-            CRF_SYM_CASE(KendallLauncher, 112, 1);
-            CRF_SYM_CASE(KendallLauncher, 128, 1);
-            default: return hipErrorNotSupported;
-        }
-    }
 #undef CRF_SYM_CASE
-    return hipGetLastError();
-}
+    }
+};
 
 }  // namespace
 
-// cs in [2, 128]; measure 1 Spearman, 2 Kendall, 3 / 5 binned MI / its correlation coefficient; hipErrorNotSupported
-// otherwise (the caller then uses direct_symmetric_kernel)
-hipError_t launch_sorted_symmetric(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                   size_t num_voxels, int measure, int num_bins, float min_x, float max_x, float min_y,
-                                   float max_y, const double* d_tables, float* d_out, hipStream_t s) {
-    if (cs < 2 || cs > kMaxSortMembers) return hipErrorNotSupported;
-    if (measure == 3 || measure == 5)
-        return launch_sorted_symmetric_binned(d_members_x, d_members_y, cs, num_voxels, measure, num_bins, min_x, max_x,
-                                              min_y, max_y, d_tables, d_out, s);
-    if (measure != 1 && measure != 2) return hipErrorNotSupported;
-    return launch_sorted_rank(d_members_x, d_members_y, cs, num_voxels, measure, d_out, num_voxels,
-                              RequestArgs{nullptr, 0, 0, 0}, s);
-}
-
-// Pair requests (crf_compute_requests) through the same kernels: Spearman / Kendall, cs in [2, 128]; X = members_i at
-// voxel i, Y = members_j at voxel j of each request; hipErrorNotSupported otherwise (-> pair_request_kernel)
-hipError_t launch_sorted_requests(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs, int ys,
-                                  size_t num_voxels, const uint32_t* d_requests, size_t num_requests, int measure,
-                                  int use_abs, float* d_out, hipStream_t s) {
-    if (cs < 2 || cs > kMaxSortMembers || (measure != 1 && measure != 2) || !d_requests) return hipErrorNotSupported;
-    if (num_requests == 0) return hipSuccess;
-    return launch_sorted_rank(d_members_i, d_members_j, cs, num_voxels, measure, d_out, num_requests,
-                              RequestArgs{d_requests, xs, ys, use_abs}, s);
+// Spearman and Kendall between two vectors per item, 2 <= cs <= kMaxSortMembers, both modes
+hipError_t launch_sorted_rank(const TwoVectorJob& job, hipStream_t s) {
+    if ((job.measure != CRF_SPEARMAN && job.measure != CRF_KENDALL) || !two_vector_sortable(job.measure, job.cs, 0))
+        return hipErrorInvalidValue;
+    if (job.measure == CRF_SPEARMAN)
+        RankMeasure<CRF_SPEARMAN>::launch(job, s);
+    else
+        RankMeasure<CRF_KENDALL>::launch(job, s);
+    return hipGetLastError();
 }
 
 }  // namespace crf

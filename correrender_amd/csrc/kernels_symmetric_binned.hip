@@ -1,24 +1,14 @@
 // kernels_symmetric_binned.hip -- binned mutual information of the SEPARATE_SYMMETRIC field mode (see
-// kernels_symmetric.hip; its own translation unit so that the two compile side by side).
+// kernels_symmetric.hip; its own translation unit so that the two compile side by side), in both two-vector modes;
+// which evaluations arrive here: two_vector_route.h.
 //   codes b1 << 8 | b0 sorted -> joint cells and Y bins as runs; the low bytes sorted again -> X bins.
 //   Voxels with skipped samples (NaN after normalisation) take the O(cs^2) path over the LDS code column.
 #include <cstdlib>
 
-#include "crf_device.h"
-#include "crf_internal.h"
 #include "crf_mi_device.h"
+#include "crf_two_vector_device.h"
 
 namespace crf {
-
-namespace {
-
-// the first N - 16 slots are members whatever cs is: the launcher picks the smallest multiple of 16 that holds cs
-template <int N>
-constexpr int sure_slots() {
-    return N - 16;
-}
-
-}  // namespace
 
 struct SymmetricSortBinnedArgs {
     int num_bins;  // <= 255
@@ -29,11 +19,6 @@ struct SymmetricSortBinnedArgs {
 // REQ: pair-request mode (crf_compute_requests; request layout {xi, yi, zi, i, xj, yj, zj, j}, HEBChart.hpp:166-168):
 // X = the members at voxel i, Y = the members at voxel j, both normalised with the PAIR's own extrema over the 2 cs
 // values (HEBChartCorrelation.cpp:493-600), cached loads, optional |.|.
-struct BinnedRequestArgs {
-    const uint32_t* requests;
-    int xs, ys;
-    int use_abs;
-};
 
 // UDIV (field mode): both ranges lie in [2^-60, 2^60] (the launcher checks): the per-sample division is formed from one
 // reciprocal per evaluation with the Markstein correction, exactly as in mi_binned_kernel (kernels_binned.hip: rcp_q)
@@ -43,16 +28,15 @@ __global__ __launch_bounds__(64, MIN_WAVES) void binned_symmetric_kernel(const f
                                                                          const double* __restrict__ tableT,
                                                                          float* __restrict__ out, size_t num_voxels,
                                                                          int cs, SymmetricSortBinnedArgs ba,
-                                                                         size_t num_items, BinnedRequestArgs ra) {
+                                                                         size_t num_items, RequestArgs ra) {
     __shared__ double T[N + 1];  // T[c] = (c/cs) ln(c/cs), T[0] = 0
     __shared__ uint16_t codes[N * 64];
-    constexpr int SURE = sure_slots<N>();
     const int lane = threadIdx.x;
     for (int i = lane; i <= N; i += 64) T[i] = i <= cs ? tableT[i] : 0.0;
     __syncthreads();
     const size_t v = size_t(blockIdx.x) * 64 + lane;
     const uint32_t bytes = uint32_t(num_voxels) * 4u;
-    const auto is_member = [cs](int e) { return EXACT || e < SURE || e < cs; };
+    const auto is_member = [cs](int e) { return CRF_SLOT_IS_MEMBER(N, EXACT, e, cs); };
     const float range_x = ba.max_x - ba.min_x, range_y = ba.max_y - ba.min_y;
     const float rcp_x = UDIV ? 1.0f / range_x : 0.0f, rcp_y = UDIV ? 1.0f / range_y : 0.0f;
     const double nbd = double(ba.num_bins);
@@ -60,8 +44,12 @@ __global__ __launch_bounds__(64, MIN_WAVES) void binned_symmetric_kernel(const f
     uint32_t a[N];
     bool is_nan = false;
     int total = 0;
+    // lane_offsets<REQ> (crf_two_vector_device.h), written out: through the call the eight request-mode instantiations
+    // come out with another schedule, and two of them measured below the written-out form (16 members -2 %, 128 members
+    // -0.1 %, profiles/two_vector_refactor.md)
+    uint32_t offset_x = uint32_t(v) * 4u, offset_y = uint32_t(v) * 4u;
     if constexpr (REQ) {
-        uint32_t offset_x = kOutOfRangeOffset, offset_y = kOutOfRangeOffset;  // items past the end read 0, store nothing
+        offset_x = offset_y = kOutOfRangeOffset;  // items past the end read 0, store nothing
         if (v < num_items) {
             const uint32_t* q = ra.requests + v * 8;
             offset_x = ((q[2] * uint32_t(ra.ys) + q[1]) * uint32_t(ra.xs) + q[0]) * 4u;  // IDXS
@@ -98,13 +86,12 @@ __global__ __launch_bounds__(64, MIN_WAVES) void binned_symmetric_kernel(const f
         asm volatile("" : "+v"(nan_flag));
         is_nan = nan_flag != 0u;
     } else {
-    const uint32_t byte_offset = uint32_t(v) * 4u;
     {
         float x[N];
 #pragma unroll
         for (int e = 0; e < N; e++)
             x[e] = load_member_nt(members_x[is_member(e) ? e : cs - 1], bytes,
-                                  is_member(e) ? byte_offset : kOutOfRangeOffset);
+                                  is_member(e) ? offset_x : kOutOfRangeOffset);
 #pragma unroll
         for (int e = 0; e < N; e++) {
             const bool member = is_member(e);
@@ -133,7 +120,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void binned_symmetric_kernel(const f
 #pragma unroll
         for (int e = 0; e < N; e++)
             y[e] = load_member_nt(members_y[is_member(e) ? e : cs - 1], bytes,
-                                  is_member(e) ? byte_offset : kOutOfRangeOffset);
+                                  is_member(e) ? offset_y : kOutOfRangeOffset);
 #pragma unroll
         for (int e = 0; e < N; e++) {
             const bool member = is_member(e);
@@ -262,53 +249,44 @@ __global__ __launch_bounds__(64, MIN_WAVES) void binned_symmetric_kernel(const f
 
 namespace {
 
-template <template <int, bool, int> class Launcher, int N, int WAVES, class... Args>
-void launch_exact_or_guarded(int cs, Args... args) {
-    if (cs == N)
-        Launcher<N, true, WAVES>::launch(args...);
-    else
-        Launcher<N, false, WAVES>::launch(args...);
-}
-
 template <int N, bool EXACT, int WAVES>
 struct BinnedLauncher {
-    static void launch(const float* const* mx, const float* const* my, const double* tableT, float* out,
-                       size_t num_voxels, int cs, SymmetricSortBinnedArgs ba, size_t num_items, BinnedRequestArgs ra,
-                       hipStream_t s) {
-        const dim3 grid(unsigned((num_items + 63) / 64));
-        if (ra.requests) {
+    static void launch(const TwoVectorJob& j, hipStream_t s) {
+        const dim3 grid(unsigned((j.num_items + 63) / 64));
+        const SymmetricSortBinnedArgs ba{j.num_bins, j.min_x, j.max_x, j.min_y, j.max_y, j.measure == CRF_BINNED_MI_CC};
+        const double* tableT = j.tables + (j.cs + 1);
+        if (j.requests) {
             // request mode holds both vectors' samples at once (2 N + N registers): one wave fewer than field mode
             constexpr int RW = WAVES > 1 ? WAVES - 1 : 1;
-            if constexpr (!EXACT)
-                hipLaunchKernelGGL((binned_symmetric_kernel<N, false, RW, true>), grid, dim3(64), 0, s, mx, my, tableT,
-                                   out, num_voxels, cs, ba, num_items, ra);
+            if constexpr (!EXACT)  // and builds the guarded instantiations only
+                hipLaunchKernelGGL((binned_symmetric_kernel<N, false, RW, true>), grid, dim3(64), 0, s, j.members_x,
+                                   j.members_y, tableT, j.out, j.num_voxels, j.cs, ba, j.num_items, request_args(j));
         } else {
             const float rx = ba.max_x - ba.min_x, ry = ba.max_y - ba.min_y;  // the kernel's own fp32 subtractions
             const char* plain = getenv("CRF_BINNED_PLAIN_DIV");              // tuning / tests
             const bool udiv = rx >= 0x1p-60f && rx <= 0x1p60f && ry >= 0x1p-60f && ry <= 0x1p60f && !(plain && *plain == '1');
             if (udiv)
-                hipLaunchKernelGGL((binned_symmetric_kernel<N, EXACT, WAVES, false, true>), grid, dim3(64), 0, s, mx, my,
-                                   tableT, out, num_voxels, cs, ba, num_items, ra);
+                hipLaunchKernelGGL((binned_symmetric_kernel<N, EXACT, WAVES, false, true>), grid, dim3(64), 0, s,
+                                   j.members_x, j.members_y, tableT, j.out, j.num_voxels, j.cs, ba, j.num_items,
+                                   request_args(j));
             else
-                hipLaunchKernelGGL((binned_symmetric_kernel<N, EXACT, WAVES, false, false>), grid, dim3(64), 0, s, mx, my,
-                                   tableT, out, num_voxels, cs, ba, num_items, ra);
+                hipLaunchKernelGGL((binned_symmetric_kernel<N, EXACT, WAVES, false, false>), grid, dim3(64), 0, s,
+                                   j.members_x, j.members_y, tableT, j.out, j.num_voxels, j.cs, ba, j.num_items,
+                                   request_args(j));
         }
     }
 };
 
 }  // namespace
 
-namespace {
-
-hipError_t launch_sorted_binned(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                size_t num_voxels, const SymmetricSortBinnedArgs& ba, const double* d_tables, float* d_out,
-                                size_t num_items, const BinnedRequestArgs& ra, hipStream_t s) {
-    const int n = (cs + 15) / 16 * 16;
-    const int cs_sel = ra.requests ? -1 : cs;  // request mode: the guarded instantiations only
-    const double* tableT = d_tables + (cs + 1);
+// binned MI / its correlation coefficient between two vectors per item, 2 <= cs <= kMaxSortMembers, 1..255 bins, both modes
+hipError_t launch_sorted_binned(const TwoVectorJob& job, hipStream_t s) {
+    if ((job.measure != CRF_MI_BINNED && job.measure != CRF_BINNED_MI_CC) ||
+        !two_vector_sortable(job.measure, job.cs, job.num_bins))
+        return hipErrorInvalidValue;
 #define CRF_SYM_CASE(N, W) \
-    case N: launch_exact_or_guarded<BinnedLauncher, N, W>(cs_sel, d_members_x, d_members_y, tableT, d_out, num_voxels, cs, ba, num_items, ra, s); break
-    switch (n) {
+    case N: launch_exact_or_guarded<BinnedLauncher, N, W>(job, s); break
+    switch ((job.cs + 15) / 16 * 16) {
         CRF_SYM_CASE(16, 4);
         CRF_SYM_CASE(32, 3);
         CRF_SYM_CASE(48, 3);
@@ -316,36 +294,10 @@ hipError_t launch_sorted_binned(const float* const* d_members_x, const float* co
         CRF_SYM_CASE(80, 2);
         CRF_SYM_CASE(96, 2);
         CRF_SYM_CASE(112, 2);
-        CRF_SYM_CASE(128, 2);
-        default: return hipErrorNotSupported;
+        default: launch_exact_or_guarded<BinnedLauncher, 128, 2>(job, s); break;
     }
 #undef CRF_SYM_CASE
     return hipGetLastError();
-}
-
-}  // namespace
-
-hipError_t launch_sorted_symmetric_binned(const float* const* d_members_x, const float* const* d_members_y, int cs,
-                                          size_t num_voxels, int measure, int num_bins, float min_x, float max_x,
-                                          float min_y, float max_y, const double* d_tables, float* d_out, hipStream_t s) {
-    if (cs < 2 || cs > kMaxSortMembers || (measure != 3 && measure != 5)) return hipErrorNotSupported;
-    if (num_bins < 1 || num_bins > 255) return hipErrorNotSupported;
-    const SymmetricSortBinnedArgs ba{num_bins, min_x, max_x, min_y, max_y, measure == 5};
-    return launch_sorted_binned(d_members_x, d_members_y, cs, num_voxels, ba, d_tables, d_out, num_voxels,
-                                BinnedRequestArgs{nullptr, 0, 0, 0}, s);
-}
-
-// binned MI / its correlation coefficient for pair requests; hipErrorNotSupported -> pair_request_kernel
-hipError_t launch_sorted_requests_binned(const float* const* d_members_i, const float* const* d_members_j, int cs, int xs,
-                                         int ys, size_t num_voxels, const uint32_t* d_requests, size_t num_requests,
-                                         int measure, int num_bins, int use_abs, const double* d_tables, float* d_out,
-                                         hipStream_t s) {
-    if (cs < 2 || cs > kMaxSortMembers || (measure != 3 && measure != 5) || !d_requests) return hipErrorNotSupported;
-    if (num_bins < 1 || num_bins > 255) return hipErrorNotSupported;
-    if (num_requests == 0) return hipSuccess;
-    const SymmetricSortBinnedArgs ba{num_bins, 0.f, 0.f, 0.f, 0.f, measure == 5};
-    return launch_sorted_binned(d_members_i, d_members_j, cs, num_voxels, ba, d_tables, d_out, num_requests,
-                                BinnedRequestArgs{d_requests, xs, ys, use_abs}, s);
 }
 
 }  // namespace crf

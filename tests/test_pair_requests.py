@@ -120,13 +120,18 @@ def test_gpu_two_field_pair_requests(engine, oracle, cs):
     with pytest.raises(CorrFieldError):
         engine.compute_requests(Measure.PEARSON, pairs, query_from_secondary=True)
     engine.upload_secondary_members(second)
+    two_vector = cs <= 128         # the two-vector kernels of the symmetric field mode, else (and for Kraskov) the counting kernel
     for m, om in ((Measure.PEARSON, 0), (Measure.SPEARMAN, 1), (Measure.KENDALL, 2)):
         assert_bit_exact(engine.compute_requests(m, pairs, query_from_secondary=True),
                          oracle.pair_requests(om, stacked, ii, jj2), f"two-field pairs {m.name} cs={cs}")
+        assert engine.last_kernel_name() == (("pearson_request_kernel" if om == 0 else "sorted_request_kernel")
+                                             if two_vector else "pair_request_kernel")
     assert_close(engine.compute_requests(Measure.MUTUAL_INFORMATION_BINNED, pairs, num_bins=60, query_from_secondary=True),
                  oracle.pair_requests(3, stacked, ii, jj2, num_bins=60), f"two-field pairs binned cs={cs}")
+    assert engine.last_kernel_name() == ("sorted_request_kernel" if two_vector else "pair_request_kernel")
     k = min(3, cs - 1)
     assert_close(engine.compute_requests(Measure.MUTUAL_INFORMATION_KRASKOV, pairs, k=k, query_from_secondary=True),
                  oracle.pair_requests(4, stacked, ii, jj2, k=k), f"two-field pairs kraskov cs={cs}")
+    assert engine.last_kernel_name() == "pair_request_kernel"
     # without the flag the second field is not read
     assert_bit_exact(engine.compute_requests(Measure.KENDALL, pairs), oracle.pair_requests(2, ens, ii, jj), "one-field pairs")

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """Development tool: throughput of the pair-request mode (crf_compute_requests_device) -- random voxel pairs."""
+import argparse
 import sys
 import time
 from pathlib import Path
@@ -11,9 +12,14 @@ import torch
 import correrender_amd as ca
 from correrender_amd._lib import CrfParams
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--members", type=int, nargs="*", default=[32, 64, 100])
+ap.add_argument("--measures", nargs="*", default=["pearson", "spearman", "kendall", "mi_binned", "mi_kraskov"])
+args = ap.parse_args()
+
 xs = ys = zs = 128
 n_req = 1 << 20
-for cs in (32, 64, 100):
+for cs in args.members:
     eng = ca.CorrField(0)
     eng.set_grid(xs, ys, zs, cs)
     members = torch.empty((cs, zs, ys, xs), dtype=torch.float32, device="cuda")
@@ -28,7 +34,7 @@ for cs in (32, 64, 100):
     d_req = torch.from_numpy(req.view(np.int32)).cuda()
     out = torch.empty(n_req, dtype=torch.float32, device="cuda")
     row = []
-    for name in ("pearson", "spearman", "kendall", "mi_binned", "mi_kraskov"):
+    for name in args.measures:
         p = CrfParams()
         p.measure = ca.MEASURE_IDS.index(name)
         p.k = 3
