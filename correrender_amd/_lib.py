@@ -53,6 +53,7 @@ SYMBOLS = {
     "crf_destroy": (None, [_VOIDP]),
     "crf_last_error": (C.c_char_p, [_VOIDP]),
     "crf_set_grid": (C.c_int, [_VOIDP, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "crf_window_count": (C.c_int, [_VOIDP]),
     "crf_upload_members": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),
     "crf_bind_members_device": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),
     "crf_upload_members_format": (C.c_int, [_VOIDP, C.c_int, C.POINTER(_VOIDP)]),

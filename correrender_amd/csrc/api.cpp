@@ -480,20 +480,20 @@ int ensure_out(crf_context* c) {  // device result of the host-output calls
     return CRF_OK;
 }
 
-// ---- member volumes of 4 GiB and more: evaluation in windows ----------------------------------------------------------
-constexpr size_t kWindowVoxels = size_t(1) << 29;  // 2 GiB of every member per launch
-
+// ---- member volumes of 4 GiB and more: evaluation in windows (the arithmetic: crf_windows.h) --------------------------
 int ensure_windows(crf_context* c) {
     crf_grid_state& g = c->grid;
     if (g.windows > 0) return CRF_OK;
-    const int windows = int((c->alloc_voxels + kWindowVoxels - 1) / kWindowVoxels);
+    const int windows = crf_window_count(c);
     const bool sec = !g.secondary.ptrs.empty();
     std::vector<const float*> table(size_t(windows) * size_t(c->cs) * (sec ? 2 : 1));
-    for (int w = 0; w < windows; w++)
+    for (int w = 0; w < windows; w++) {
+        const size_t first = crf::window_first(size_t(w), c->window_voxels);
         for (int m = 0; m < c->cs; m++) {
-            table[(size_t(w) * (sec ? 2 : 1)) * size_t(c->cs) + size_t(m)] = g.members.f32(m) + size_t(w) * kWindowVoxels;
-            if (sec) table[(size_t(w) * 2 + 1) * size_t(c->cs) + size_t(m)] = g.secondary.f32(m) + size_t(w) * kWindowVoxels;
+            table[(size_t(w) * (sec ? 2 : 1)) * size_t(c->cs) + size_t(m)] = g.members.f32(m) + first;
+            if (sec) table[(size_t(w) * 2 + 1) * size_t(c->cs) + size_t(m)] = g.secondary.f32(m) + first;
         }
+    }
     CRF_HIP(c, g.window_tables.reserve(table.size()));
     CRF_HIP(c, hipMemcpy(g.window_tables.get(), table.data(), table.size() * sizeof(float*), hipMemcpyHostToDevice));
     g.windows = windows;
@@ -512,8 +512,8 @@ struct NarrowScope {
         const size_t per = size_t(g.window_has_secondary ? 2 : 1) * size_t(c->cs);
         c->view.members = g.window_tables.get() + size_t(w) * per;
         if (g.window_has_secondary) c->view.secondary = g.window_tables.get() + size_t(w) * per + size_t(c->cs);
-        c->view.num_voxels = std::min(kWindowVoxels, c->alloc_voxels - size_t(w) * kWindowVoxels);
-        return size_t(w) * kWindowVoxels;
+        c->view.num_voxels = crf::window_length(c->alloc_voxels, size_t(w), c->window_voxels);
+        return crf::window_first(size_t(w), c->window_voxels);
     }
     void select_range(int j, int scratch_set) {  // range j of ensure_host_ranges, writing the scratch of its stream
         const crf_grid_state& g = c->grid;
@@ -991,6 +991,14 @@ int crf_set_grid(crf_context* c, int xs, int ys, int zs, int cs) {
     if (xs <= 0 || ys <= 0 || zs <= 0 || cs <= 0)
         return fail(c, CRF_ERR_ARGUMENT, fmt("invalid grid %dx%dx%d with %d members", xs, ys, zs, cs));
     const size_t n = size_t(xs) * size_t(ys) * size_t(zs);
+    // CRF_WINDOW_VOXELS (tests): another window size, so that a small grid takes the windowed routes (crf_windows.h)
+    // It is read here like CRF_HOST_CHUNKS and CRF_COPY_THREADS are read where they apply, but strictly: env_int_or's atoi
+    // would take "1024abc" for 1024, and a value that does not count must fail, not fall back.
+    const char* window_text = getenv("CRF_WINDOW_VOXELS");
+    const long long window_override = crf::parse_window_override(window_text);
+    if (window_override < 0)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("CRF_WINDOW_VOXELS=%.64s is neither 0 nor a positive multiple of %zu voxels up to %zu",
+                                             window_text, crf::kWindowGranule, crf::kMaxWindowVoxels));
     if (int r = bind_device(c)) return r;
     CRF_HIP(c, hipDeviceSynchronize());  // evaluations the caller left in flight on its own streams still read the scratch
     c->grid = crf_grid_state{};  // the members, everything derived from them and everything sized for the old grid
@@ -1002,9 +1010,11 @@ int crf_set_grid(crf_context* c, int xs, int ys, int zs, int cs) {
     c->alloc_voxels = n;
     // The kernels address a member with 32-bit byte offsets, and their out-of-range sentinel offset (crf_device.h
     // kOutOfRangeOffset = 0xFFFFFFF0) must lie beyond the end of every member: a member volume of 4 GiB or more (1024^3 is
-    // exactly 4 GiB; the reference has no limit) is evaluated in WINDOWS of kWindowVoxels voxels, one launch each, through
-    // member-pointer tables advanced by the window's first voxel (ensure_windows below).
-    c->windowed = n * sizeof(float) >= size_t(0xFFFFFFF0u);
+    // exactly 4 GiB; the reference has no limit) is evaluated in WINDOWS of 2^29 voxels, one launch each, through
+    // member-pointer tables advanced by the window's first voxel (ensure_windows above; the rule and the override:
+    // crf_windows.h).  Both are captured here for the life of this grid.
+    c->windowed = crf::grid_windowed(n, size_t(window_override));
+    c->window_voxels = crf::window_voxels(size_t(window_override));
     CRF_HIP(c, c->grid.members.table.reserve(size_t(cs)));
     CRF_HIP(c, c->grid.narrow.table.reserve(size_t(cs)));
     CRF_HIP(c, c->grid.ref.reserve(size_t(cs)));
@@ -1013,6 +1023,11 @@ int crf_set_grid(crf_context* c, int xs, int ys, int zs, int cs) {
     CRF_HIP(c, hipMemcpy(c->grid.tables.get(), tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice));
     c->view = whole_view(c);
     return CRF_OK;
+}
+
+int crf_window_count(const crf_context* c) {
+    if (!c) return 0;
+    return c->windowed ? int(crf::windows_covering(c->alloc_voxels, c->window_voxels)) : 1;
 }
 
 int crf_set_kraskov_noise(crf_context* c, const double* ref_noise, const double* query_noise) {
@@ -1469,7 +1484,7 @@ int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, v
     if (estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 && (k < 1 || k >= c->cs))
         return fail(c, CRF_ERR_ARGUMENT, fmt("k=%d must be in [1, cs-1=%d]", k, c->cs - 1));
     if (int r = bind_device(c)) return r;
-    if (int r = ensure_workspace(c, crf::dkl_workspace_bytes(c->cs, estimator, num_bins, std::min(c->view.num_voxels, kWindowVoxels)))) return r;
+    if (int r = ensure_workspace(c, crf::dkl_workspace_bytes(c->cs, estimator, num_bins, std::min(c->view.num_voxels, c->window_voxels)))) return r;
     // psi(n) = -gamma + H_{n-1} (boost::math::digamma at positive integers, DKL.cpp:156)
     const double knn_const =
         estimator == CRF_DKL_ENTROPY_KNN && c->cs > 1 ? psi_int(c->cs) - psi_int(k) + std::log(2.0) : 0.0;

@@ -14,6 +14,7 @@
 #include "crf_internal.h"
 #include "crf_owned.h"
 #include "crf_pool.h"
+#include "crf_windows.h"
 
 // Scratch that the per-voxel kernels WRITE.  Launches that share a set must be ordered on one stream.
 struct crf_scratch {
@@ -98,7 +99,8 @@ struct crf_context {
     std::string err;
     int xs = 0, ys = 0, zs = 0, cs = 0;
     size_t alloc_voxels = 0;  // voxels of the whole local grid
-    bool windowed = false;    // member volumes of 4 GiB or more
+    bool windowed = false;    // member volumes of 4 GiB or more (or more voxels than CRF_WINDOW_VOXELS): crf_windows.h
+    size_t window_voxels = crf::kDefaultWindowVoxels;  // voxels of a full window, captured by crf_set_grid for this grid
     crf_grid_state grid;
     crf_launch_view view;
     int last_format = CRF_MEMBER_F32;  // what the per-voxel kernel of the last field evaluation read

@@ -98,6 +98,11 @@ class CorrField:
         self.cs = cs
         self._keepalive = None
 
+    def window_count(self) -> int:
+        """Launches a per-voxel evaluation of the current grid takes: 1 for an ordinary grid, more for one whose member
+        volumes are 4 GiB or larger (evaluated in windows: the slower path).  Valid right after set_grid."""
+        return int(self._lib.crf_window_count(self._ctx))
+
     def upload_members(self, members: Sequence[np.ndarray]):
         """members: cs host arrays of zs*ys*xs elements (any shape, C-contiguous, x fastest).  Arrays that are all
         float16, uint16 or uint8 stay in that format on the device (value = float(h), s / 65535, b / 255: the reference's

@@ -128,13 +128,19 @@ const char* crf_last_error(const crf_context* ctx);
 /* ABI version of this header, bumped on incompatible change. */
 int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_minmax_divergent; added since, compatibly:
                                   crf_upload_members_format, crf_bind_members_device_format, crf_member_format,
-                                  crf_last_member_format, crf_wide_copy_bytes;
+                                  crf_last_member_format, crf_wide_copy_bytes, crf_window_count;
                                4: crf_group_* (several devices behind one caller thread), crf_set_kraskov_noise;
                                3: crf_params.reserved[0] became prepared_slot (same layout; 0 keeps the old meaning) */
 
 /* ---- the ensemble (replaces the fields[] gather of CorrelationCalculator.cpp:791-800) --------------------- */
 /* Declares the LOCAL grid (a whole grid, or this process's z-slab of one) and member count; drops any members. */
 int crf_set_grid(crf_context* ctx, int xs, int ys, int zs, int cs);
+/* The launches a per-voxel evaluation of the current local grid takes: 1 for an ordinary grid; 2 or more for a grid
+ * whose fp32 member volume is 4 GiB or more, which is evaluated in windows of 2^29 voxels (the slower path: no native
+ * narrow-format route, no packed Pearson copy, no range pipeline of crf_compute; pair requests and crf_tile_field_device
+ * are refused).  Valid right after crf_set_grid; 0 if ctx == NULL.  (Tests set CRF_WINDOW_VOXELS, read by crf_set_grid,
+ * to a positive multiple of 1024 to window a small grid: it is then windowed iff it has more voxels than that.) */
+int crf_window_count(const crf_context* ctx);
 /* Copies cs host volumes (each xs*ys*zs floats) into HBM owned by the context (the role the reference's LRU
  * field cache plays across reference-point moves, VolumeData.cpp:1202-1226). */
 int crf_upload_members(crf_context* ctx, const float* const* host_members);
