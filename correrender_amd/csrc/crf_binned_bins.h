@@ -7,7 +7,7 @@
 // Two forms of q, which the launchers choose between per evaluation (range = max - min is the same for every sample):
 //   division     q = d / range,  d = y - min;  the sample counts iff q is not NaN
 //   reciprocal   rcp = RN(1 / range) once;  q0 = RN(d * rcp);  q = fma(fma(-q0, range, d), rcp, q0);  counts iff d == d
-// The reciprocal form is the correctly rounded d / range whenever the remainder is exact (Markstein; crf_device.h:
+// The reciprocal form is the correctly rounded d / range whenever the remainder is exact (Markstein; crf_exact_div.h:
 // exact_div).  Where it is not -- |d| < 2^-100, or a quotient that leaves the normal range -- the quotient is below 2^-40
 // or infinite either way and lands in the same bin (0) as the division's; for d = +-inf (or an overflowing q0) the chain
 // yields NaN where the division yields +-inf: both convert to bin 0 (bin_index_x86), and whether the sample counts is

@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "crf_binned_bins.h"  // bin_index_x86 and the per-sample bin of binned MI (host-usable)
+#include "crf_exact_div.h"    // exact_div, exact_div_guard (host-usable)
 #include "crf_internal.h"
 
 namespace crf {
@@ -385,22 +386,7 @@ __device__ __forceinline__ void pin_array(T (&a)[N]) {
     for (int i = 0; i < N; i++) asm volatile("" : "+v"(a[i]));
 }
 
-// Correctly rounded fp32 quotients a/b for MANY numerators and ONE denominator (the voxel's standard deviation) without
-// the ~10-instruction IEEE division expansion per element: with rcp = RN(1/b) (one true division),
-//     q0 = RN(a * rcp);  rem = fma(-q0, b, a) (exact);  q = fma(rem, rcp, q0)
-// is the correctly rounded a/b (Markstein's theorem; checked against `/` on 2.4e9 operand pairs including every
-// significand of b) PROVIDED rem is exactly representable, i.e. no underflow: |a| >= 2^-100 or a == 0, b in
-// [2^-60, 2^60].  In the Pearson tail a = y_e - mean: a non-zero difference of two floats is at least half an ulp of
-// the mean, so |mean| >= 2^-70 guarantees the bound on every a.  exact_div_guard() is that per-voxel test; when it
-// fails for any lane of the wave the kernels take the plain-division path.
-__device__ __forceinline__ bool exact_div_guard(float mean, float sd) {
-    return fabsf(mean) >= 0x1p-70f && sd >= 0x1p-60f && sd <= 0x1p60f;  // false for NaN, 0, inf, tiny
-}
-__device__ __forceinline__ float exact_div(float a, float b, float rcp) {
-    const float q0 = a * rcp;
-    const float rem = fmaf(-q0, b, a);
-    return fmaf(rem, rcp, q0);
-}
+// exact_div / exact_div_guard: crf_exact_div.h
 
 // The value the calculators see of ONE stored code that a kernel holds in a register (load_code_nt): narrow_value's
 // operations, the integer formats' quotient through exact_div with a compile-time reciprocal (an integer below 2^16 over

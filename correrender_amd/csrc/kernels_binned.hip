@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64, MIN_WAVES) void mi_binned_kernel(const float* c
     const double nbd = double(nb);
     // (y - min) / range with ONE true division per evaluation: range is the same for every sample, and with
     // rcp = RN(1 / range) the quotient q = fma(fma(-q0, range, d), rcp, q0), q0 = RN(d * rcp), is the correctly rounded
-    // d / range (Markstein; crf_device.h: exact_div) whenever the remainder is exact.  Where it is not -- |d| < 2^-100,
+    // d / range (Markstein; crf_exact_div.h: exact_div) whenever the remainder is exact.  Where it is not -- |d| < 2^-100,
     // or a quotient that leaves the normal range -- the quotient is below 2^-40 or infinite either way and lands in the
     // same bin (0) as the division's; for d = +-inf (or an overflowing q0) the chain yields NaN where the division
     // yields +-inf: both convert to bin 0 (bin_index_x86), and whether the sample counts is decided from the sample

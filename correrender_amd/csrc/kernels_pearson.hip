@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_reg_kernel(const float
     bool guard = true;
 #pragma unroll
     for (int v = 0; v < VPT; v++) guard = guard && exact_div_guard(meanY[v], sdY[v]);
-    if (__all(guard)) {  // exact quotients through one reciprocal per voxel (crf_device.h: exact_div)
+    if (__all(guard)) {  // exact quotients through one reciprocal per voxel (crf_exact_div.h: exact_div)
         float rcp[VPT];
 #pragma unroll
         for (int v = 0; v < VPT; v++) rcp[v] = 1.0f / sdY[v];
@@ -293,7 +293,7 @@ __device__ __forceinline__ void pearson_packed_wave(const float* const* __restri
     }
     const float sdY = sqrtf(varY);
     float r = 0.0f;
-    if (__all(exact_div_guard(meanY, sdY))) {  // exact_div (crf_device.h) two slots at a time, then r += a_e * q_e
+    if (__all(exact_div_guard(meanY, sdY))) {  // exact_div (crf_exact_div.h) two slots at a time, then r += a_e * q_e
         const float rcp = 1.0f / sdY;
         const f2 rcp2 = {rcp, rcp}, sd2 = {sdY, sdY};
 #pragma unroll
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_split_kernel(const flo
     const float sdY = sqrtf(from_lane(var, last_group_lane));
     // ---- pass 3: r += a_e * (d_e / sdY)
     float r = 0.0f;
-    // exact_div needs sd in [2^-60, 2^60] and every non-zero deviation >= 2^-100 in magnitude (crf_device.h).
+    // exact_div needs sd in [2^-60, 2^60] and every non-zero deviation >= 2^-100 in magnitude (crf_exact_div.h).
     // exact_div_guard() infers the latter from |mean| >= 2^-70; a wave in which that fails -- a mean that is exactly 0
     // is enough, and the benchmark's box ensemble has such voxels at 512 members -- looks at its deviations themselves
     // before it gives up the exact path, whose alternative is expensive here (see the else branch).
@@ -724,7 +724,7 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_split_kernel(const flo
 // one member is still 256 contiguous bytes, all cs loads are issued before the first use, and the cs raw dwords stay in
 // registers for the three passes: cs VGPRs for 2 or 4 voxels where the fp32 kernel needs cs per voxel.  Each pass
 // converts on use -- y_e - meanY recomputed in pass 3 from the same operands is the same float as the one pass 2 saw.
-// The integer formats' value x / 255.0f, x / 65535.0f is exact_div (crf_device.h) with a compile-time reciprocal: x is
+// The integer formats' value x / 255.0f, x / 65535.0f is exact_div (crf_exact_div.h) with a compile-time reciprocal: x is
 // an integer below 2^16 and the denominator a constant inside [2^-60, 2^60], its preconditions.  Everything is done
 // two voxels at a time in packed fp32 (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32: the same IEEE operation per element,
 // contraction off), as in pearson_split_kernel; the sequential sums are one chain per voxel, element-wise.
@@ -814,7 +814,7 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_narrow_kernel(const vo
         guard = guard && exact_div_guard(meanY[p][0], sdY[p][0]) && exact_div_guard(meanY[p][1], sdY[p][1]);
     }
     // pass 3: r += a_e * (d_e / sdY)
-    if (__all(guard)) {  // exact quotients through one reciprocal per voxel (crf_device.h: exact_div)
+    if (__all(guard)) {  // exact quotients through one reciprocal per voxel (crf_exact_div.h: exact_div)
         f2 rcp[P];
 #pragma unroll
         for (int p = 0; p < P; p++) rcp[p] = f2{1.0f / sdY[p][0], 1.0f / sdY[p][1]};
