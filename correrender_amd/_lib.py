@@ -66,6 +66,10 @@ SYMBOLS = {
     "crf_upload_secondary_members": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),
     "crf_bind_secondary_members_device": (C.c_int, [_VOIDP, C.POINTER(_VOIDP)]),
     "crf_secondary_member_minmax": (C.c_int, [_VOIDP, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "crf_upload_secondary_members_format": (C.c_int, [_VOIDP, C.c_int, C.POINTER(_VOIDP)]),
+    "crf_bind_secondary_members_device_format": (C.c_int, [_VOIDP, C.c_int, C.POINTER(_VOIDP)]),
+    "crf_secondary_member_format": (C.c_int, [_VOIDP]),
+    "crf_secondary_wide_copy_bytes": (C.c_size_t, [_VOIDP]),
     "crf_gather_reference": (C.c_int, [_VOIDP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "crf_gather_reference_device": (C.c_int, [_VOIDP, C.c_int, C.c_int, C.c_int, _VOIDP, _VOIDP]),
     "crf_gather_reference_rows_device": (C.c_int, [_VOIDP, C.POINTER(C.c_int32), C.c_int, _VOIDP, _VOIDP]),

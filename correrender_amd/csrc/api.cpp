@@ -72,7 +72,24 @@ const char* format_name(int format) {
 // what a launch on the whole local grid reads
 crf_launch_view whole_view(const crf_context* c) {
     const crf_grid_state& g = c->grid;
-    return {g.members.f32_table(), g.secondary.f32_table(), g.narrow.table.get(), c->alloc_voxels, g.members.vpt, 0};
+    return {g.members.f32_table(), g.secondary.f32_table(), g.narrow.table.get(), c->alloc_voxels, g.members.vpt, 0,
+            g.secondary_narrow.table.get()};
+}
+
+// One scalar field's members as the context holds them (crf_context.h): the fp32 set, the narrow set, the format that
+// says which of the two the caller gave, and the fp32 copy of narrow ones.  Non-owning.
+struct FieldMembers {
+    crf_member_set& f32;
+    crf_member_set& narrow;
+    int& format;
+    crf::DeviceBuffer<float>& wide;
+    const char* label;  // how a message names the field's members
+    crf_member_set& current() const { return format == CRF_MEMBER_F32 ? f32 : narrow; }
+};
+FieldMembers field_members(crf_context* c, bool secondary) {
+    crf_grid_state& g = c->grid;
+    if (secondary) return {g.secondary, g.secondary_narrow, g.secondary_format, g.secondary_wide, "secondary members"};
+    return {g.members, g.narrow, g.format, g.wide, "members"};
 }
 
 // ---- what is derived from the members, and what drops it ---------------------------------------------------------------
@@ -82,6 +99,8 @@ crf_launch_view whole_view(const crf_context* c) {
 //   window tables                          ensure_windows       the pointers of `members` and of `secondary`
 //   packed copy                            ensure_packed        the values of `members`
 //   wide copy (`members` of narrow ones)   ensure_wide          the values of `narrow`
+//   secondary wide copy (`secondary` of    ensure_secondary_wide  the values of `secondary_narrow`
+//     narrow secondary members)
 // Each function below is the whole answer to "what goes when this changes"; crf_set_grid drops everything by replacing
 // the grid state.
 
@@ -111,9 +130,19 @@ void primary_members_changed(crf_context* c) {
     }
 }
 
+// The fp32 view of narrow secondary members appeared (ensure_secondary_wide): the window tables are the one derived object
+// that reads the secondary's fp32 pointers.
+void secondary_fp32_view_appeared(crf_context* c) { c->grid.windows = 0; }
+
+// The secondary members were replaced or overwritten in place.  The one place that drops their wide copy.
 void secondary_members_changed(crf_context* c) {
-    c->grid.secondary.minmax_valid = false;
-    c->grid.windows = 0;
+    crf_grid_state& g = c->grid;
+    g.secondary.minmax_valid = g.secondary_narrow.minmax_valid = false;
+    g.windows = 0;
+    if (g.secondary_format != CRF_MEMBER_F32) {  // the wide copy, and the fp32 pointers into it
+        g.secondary_wide.reset();
+        g.secondary.ptrs.clear();
+    }
 }
 
 // the set's alignment facts and its device table, from set.ptrs
@@ -134,7 +163,7 @@ int install_table(crf_context* c, crf_member_set& set) {
     return CRF_OK;
 }
 
-// Replaces the primary members (secondary == false; any format) or the secondary ones (fp32) by cs volumes uploaded from
+// Replaces the primary members (secondary == false) or the secondary ones, in any format, by cs volumes uploaded from
 // host memory into one owned block, or bound where they lie in device memory.  label: how the messages name a member.
 int set_members(crf_context* c, bool secondary, int format, const void* const* members, bool upload, const char* label) {
     if (!c || !members) return fail(c, CRF_ERR_ARGUMENT, "null argument");
@@ -148,17 +177,12 @@ int set_members(crf_context* c, bool secondary, int format, const void* const* m
         return fail(c, CRF_ERR_UNSUPPORTED, fmt("%s members of 4 GiB or more are not supported (%zu voxels per member)",
                                                 format_name(format), c->alloc_voxels));
     if (int r = bind_device(c)) return r;
-    crf_grid_state& g = c->grid;
-    if (secondary) {
-        secondary_members_changed(c);
-        g.secondary.clear();
-    } else {
-        primary_members_changed(c);
-        g.members.clear();
-        g.narrow.clear();
-        g.format = format;
-    }
-    crf_member_set& set = secondary ? g.secondary : format == CRF_MEMBER_F32 ? g.members : g.narrow;
+    (secondary ? secondary_members_changed : primary_members_changed)(c);
+    const FieldMembers field = field_members(c, secondary);
+    field.f32.clear();
+    field.narrow.clear();
+    field.format = format;
+    crf_member_set& set = field.current();
     set.format = format;
     if (!upload) {
         set.ptrs.assign(members, members + c->cs);
@@ -201,30 +225,36 @@ int member_minmax(crf_context* c, crf_member_set& set, float* out_min, float* ou
 // Narrow members: the fp32 copy for every evaluation without a native route (native_field, native_reduction) -- one owned
 // block that `members` points into, converted on stream s at the first call that needs it.  A caller that stays on the
 // native routes, the extrema and the reference gathers never pays for it.  Dropped with the members it was made from.
-int ensure_wide(crf_context* c, hipStream_t s) {
-    crf_grid_state& g = c->grid;
-    if (g.format == CRF_MEMBER_F32 || !g.members.ptrs.empty()) return CRF_OK;
+// The same serves the secondary field: its copy is `secondary_wide`, its fp32 set `secondary` (ensure_secondary_wide).  A
+// field that is not there, or is fp32, needs nothing.
+int ensure_wide_of(crf_context* c, bool secondary, hipStream_t s) {
+    const FieldMembers field = field_members(c, secondary);
+    if (field.format == CRF_MEMBER_F32 || !field.f32.ptrs.empty() || field.narrow.ptrs.empty()) return CRF_OK;
     if (int r = bind_device(c)) return r;
     const size_t stride = (c->alloc_voxels + 63) & ~size_t(63);
-    if (g.wide.reserve(stride * size_t(c->cs)) != hipSuccess) {
+    if (field.wide.reserve(stride * size_t(c->cs)) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(c, CRF_ERR_DEVICE, fmt("no device memory for the fp32 copy of the %s members (%zu bytes)",
-                                           format_name(g.format), stride * sizeof(float) * size_t(c->cs)));
+        return fail(c, CRF_ERR_DEVICE, fmt("no device memory for the fp32 copy of the %s %s (%zu bytes)",
+                                           format_name(field.format), field.label, stride * sizeof(float) * size_t(c->cs)));
     }
-    CRF_HIP(c, crf::launch_widen_members(g.narrow.table.get(), g.format, c->cs, c->alloc_voxels, g.wide.get(), stride, s));
-    for (int i = 0; i < c->cs; i++) g.members.ptrs.push_back(g.wide.get() + stride * size_t(i));
-    g.members.vpt = 4;
-    CRF_HIP(c, hipMemcpyAsync(g.members.table.get(), g.members.ptrs.data(), sizeof(void*) * size_t(c->cs),
+    CRF_HIP(c, crf::launch_widen_members(field.narrow.table.get(), field.format, c->cs, c->alloc_voxels, field.wide.get(),
+                                         stride, s));
+    for (int i = 0; i < c->cs; i++) field.f32.ptrs.push_back(field.wide.get() + stride * size_t(i));
+    field.f32.vpt = 4;
+    CRF_HIP(c, field.f32.table.reserve(size_t(c->cs)));
+    CRF_HIP(c, hipMemcpyAsync(field.f32.table.get(), field.f32.ptrs.data(), sizeof(void*) * size_t(c->cs),
                               hipMemcpyHostToDevice, s));
     CRF_HIP(c, hipStreamSynchronize(s));
     c->view = whole_view(c);
-    fp32_view_appeared(c);
+    (secondary ? secondary_fp32_view_appeared : fp32_view_appeared)(c);
     return CRF_OK;
 }
+int ensure_wide(crf_context* c, hipStream_t s) { return ensure_wide_of(c, false, s); }
+int ensure_secondary_wide(crf_context* c, hipStream_t s) { return ensure_wide_of(c, true, s); }
 
 // Whether the per-voxel kernel of this field evaluation reads the narrow members as they are (view.narrow), no fp32 copy.
-// Everything else -- more than kNarrowMaxMembers members, the symmetric mode, windowed grids, pair requests --
-// runs on the fp32 copy (ensure_wide).  Per measure:
+// Everything else -- more than kNarrowMaxMembers members, the symmetric mode but for its Pearson route below, windowed
+// grids, pair requests -- runs on the fp32 copy (ensure_wide).  Per measure:
 //   Pearson    2..128 members, dword loads: every member 4-byte aligned (kernels_pearson.hip: pearson_narrow_kernel)
 //   Kendall    2..128 members, element loads: the element's own alignment (kernels_rank_narrow.hip)
 //   Spearman   33..128 members (kernels_rank_narrow.hip); up to 32 the fp32 kernels handle ties in line and the call stays
@@ -235,10 +265,16 @@ int ensure_wide(crf_context* c, hipStream_t s) {
 //   Kraskov MI 2..128 members, element loads, where measured no slower than the copy route (kraskov_plan.h:
 //              kraskov_narrow_plan; profiles/narrow_kraskov_ab.md).  The CRF_KRASKOV_* switches move a native call as they
 //              move an fp32 call; CRF_KRASKOV_SORTED=1 asks for the sorted-column kernel, which reads fp32
+// The symmetric mode (two fields per voxel) has one native route: the Pearson field over two fields in the SAME narrow format,
+// both sets 4-byte aligned (dword loads), at the member counts of symmetric_narrow_routed (symmetric_narrow_route.h;
+// profiles/narrow_symmetric_ab.md) -- kernels_pearson.hip: pearson_symmetric_narrow_kernel.  Every other symmetric
+// evaluation reads fp32 views of both fields (ensure_wide, ensure_secondary_wide).
 bool native_field(const crf_context* c, const crf_params* p) {
     const crf_grid_state& g = c->grid;
-    if (g.format == CRF_MEMBER_F32 || (p->flags & CRF_FLAG_SYMMETRIC) || c->cs > crf::kNarrowMaxMembers || c->windowed)
-        return false;
+    if (g.format == CRF_MEMBER_F32 || c->cs > crf::kNarrowMaxMembers || c->windowed) return false;
+    if (p->flags & CRF_FLAG_SYMMETRIC)
+        return p->measure == CRF_PEARSON && g.secondary_format == g.format && !g.secondary_narrow.ptrs.empty() &&
+               g.narrow.dword_aligned && g.secondary_narrow.dword_aligned && crf::symmetric_narrow_routed(g.format, c->cs);
     switch (p->measure) {
         case CRF_PEARSON: return c->cs >= 2 && g.narrow.dword_aligned;
         case CRF_KENDALL: return c->cs >= 2 && g.narrow.element_aligned;
@@ -605,11 +641,32 @@ int compute_symmetric(crf_context* c, const crf_params* p, float* out, hipStream
     return launch.finish(e);
 }
 
+// ... and its native route (native_field): the Pearson field over two fields in one narrow format, read as stored
+int compute_symmetric_narrow(crf_context* c, float* out, hipStream_t s) {
+    TimedLaunch launch(c);
+    const int format = c->grid.format;
+    const uintptr_t vector_bytes = format == CRF_MEMBER_U8 ? 16 : 8;  // one lane's results
+    return launch.finish(crf::launch_pearson_symmetric_narrow(c->view.narrow, c->view.secondary_narrow, format, c->cs,
+                                                              c->view.num_voxels,
+                                                              reinterpret_cast<uintptr_t>(out) % vector_bytes == 0, out, s,
+                                                              launch.e0, launch.e1, &launch.info));
+}
+
 int ref_voxel(crf_context* c, int x, int y, int z, size_t* voxel) {
     if (x < 0 || y < 0 || z < 0 || x >= c->xs || y >= c->ys || z >= c->zs)
         return fail(c, CRF_ERR_ARGUMENT,
                     fmt("reference point (%d,%d,%d) outside the local grid %dx%dx%d", x, y, z, c->xs, c->ys, c->zs));
     *voxel = (size_t(z) * size_t(c->ys) + size_t(y)) * size_t(c->xs) + size_t(x);  // IDXS, DataSet.hpp:37
+    return CRF_OK;
+}
+
+// device_out[m] = the value of secondary member m at `voxel`: narrow secondary members as stored (no fp32 copy, any alignment)
+int gather_secondary_reference(crf_context* c, size_t voxel, float* device_out, hipStream_t s) {
+    if (c->grid.secondary_format != CRF_MEMBER_F32)
+        CRF_HIP(c, crf::launch_gather_reference_narrow(c->view.secondary_narrow, c->grid.secondary_format, c->cs, voxel,
+                                                       device_out, s));
+    else
+        CRF_HIP(c, crf::launch_gather_reference(c->view.secondary, c->cs, voxel, device_out, s));
     return CRF_OK;
 }
 
@@ -704,8 +761,10 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
     if (phase & 2u) c->last_format = native ? c->grid.format : CRF_MEMBER_F32;
     if (symmetric) {
         if (phase != 3u) return fail(c, CRF_ERR_ARGUMENT, "the symmetric mode has no reference-side preparation");
-        if (c->grid.secondary.ptrs.empty())
+        if (!c->grid.has_secondary())
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_SYMMETRIC needs secondary members (crf_upload_secondary_members)");
+        if (native) return compute_symmetric_narrow(c, out, s);
+        if (int r = ensure_secondary_wide(c, s)) return r;
         return for_each_window(c, out, [&](float* o) { return compute_symmetric(c, p, o, s); });
     }
     float* prep = c->prep.get();
@@ -725,11 +784,11 @@ int compute_impl_one(crf_context* c, const crf_params* p, const void* device_ref
         ref.table = ov->table;
         ref.voxel = ov->voxel;
     } else if (!ref.values && (p->flags & CRF_FLAG_REFERENCE_FROM_SECONDARY)) {
-        if (c->grid.secondary.ptrs.empty())
+        if (!c->grid.has_secondary())
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_REFERENCE_FROM_SECONDARY needs secondary members");
         size_t voxel;
         if (int r = ref_voxel(c, p->ref_x, p->ref_y, p->ref_z, &voxel)) return r;
-        CRF_HIP(c, crf::launch_gather_reference(c->view.secondary, c->cs, voxel, c->grid.ref.get(), s));
+        if (int r = gather_secondary_reference(c, voxel, c->grid.ref.get(), s)) return r;
         ref.values = c->grid.ref.get();
     }
     if ((phase & 1u) && !ref.values && !ref.table) {
@@ -1100,11 +1159,23 @@ int crf_bind_secondary_members_device(crf_context* c, const void* const* device_
     return set_members(c, true, CRF_MEMBER_F32, device_members, false, "secondary member");
 }
 
+int crf_upload_secondary_members_format(crf_context* c, int format, const void* const* host_members) {
+    return set_members(c, true, format, host_members, true, "secondary member");
+}
+
+int crf_bind_secondary_members_device_format(crf_context* c, int format, const void* const* device_members) {
+    return set_members(c, true, format, device_members, false, "secondary member");
+}
+
+int crf_secondary_member_format(const crf_context* c) { return c ? c->grid.secondary_format : CRF_MEMBER_F32; }
+
+size_t crf_secondary_wide_copy_bytes(const crf_context* c) { return c ? c->grid.secondary_wide.count() * sizeof(float) : 0; }
+
 int crf_secondary_member_minmax(crf_context* c, float* out_min, float* out_max) {
     if (int r = check_ready(c)) return r;
     if (!out_min || !out_max) return fail(c, CRF_ERR_ARGUMENT, "null output");
-    if (c->grid.secondary.ptrs.empty()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
-    return member_minmax(c, c->grid.secondary, out_min, out_max);
+    if (!c->grid.has_secondary()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
+    return member_minmax(c, field_members(c, true).current(), out_min, out_max);
 }
 
 int crf_gather_reference_device(crf_context* c, int x, int y, int z, void* device_out, void* stream) {
@@ -1158,14 +1229,15 @@ namespace crf {
 
 int gather_reference_to(crf_context* c, bool secondary, int x, int y, int z, float* device_out, hipStream_t s) {
     if (int r = check_ready(c)) return r;
-    if (secondary && c->grid.secondary.ptrs.empty()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
+    if (secondary && !c->grid.has_secondary()) return fail(c, CRF_ERR_STATE, "no secondary members are bound");
     size_t voxel;
     if (int r = ref_voxel(c, x, y, z, &voxel)) return r;
     if (int r = bind_device(c)) return r;
-    if (!secondary && c->grid.format != CRF_MEMBER_F32)
+    if (secondary) return gather_secondary_reference(c, voxel, device_out, s);
+    if (c->grid.format != CRF_MEMBER_F32)
         CRF_HIP(c, launch_gather_reference_narrow(c->view.narrow, c->grid.format, c->cs, voxel, device_out, s));
     else
-        CRF_HIP(c, launch_gather_reference(secondary ? c->view.secondary : c->view.members, c->cs, voxel, device_out, s));
+        CRF_HIP(c, launch_gather_reference(c->view.members, c->cs, voxel, device_out, s));
     return CRF_OK;
 }
 
@@ -1178,9 +1250,9 @@ int second_stream(crf_context* c, hipStream_t* out) {
 
 int reference_override(crf_context* owner, bool secondary, int x, int y, int z, RefOverride* out) {
     if (int r = check_ready(owner)) return r;
-    if (secondary && owner->grid.secondary.ptrs.empty()) return fail(owner, CRF_ERR_STATE, "no secondary members are bound");
+    if (secondary && !owner->grid.has_secondary()) return fail(owner, CRF_ERR_STATE, "no secondary members are bound");
     if (int r = ref_voxel(owner, x, y, z, &out->voxel)) return r;
-    if (!secondary && owner->grid.format != CRF_MEMBER_F32)
+    if ((secondary ? owner->grid.secondary_format : owner->grid.format) != CRF_MEMBER_F32)
         return fail(owner, CRF_ERR_UNSUPPORTED, "a direct reference read needs fp32 members");
     out->table = secondary ? owner->view.secondary : owner->view.members;
     return CRF_OK;
@@ -1389,8 +1461,9 @@ int crf_compute_requests_device(crf_context* c, const crf_params* p, const void*
     crf::TwoVectorJob job = two_vector_job(c, p);
     // two-field request mode: the j side reads the secondary members (CRF_FLAG_QUERY_FROM_SECONDARY)
     if (p->flags & CRF_FLAG_QUERY_FROM_SECONDARY) {
-        if (c->grid.secondary.ptrs.empty())
+        if (!c->grid.has_secondary())
             return fail(c, CRF_ERR_STATE, "CRF_FLAG_QUERY_FROM_SECONDARY needs secondary members (crf_upload_secondary_members)");
+        if (int r = ensure_secondary_wide(c, s)) return r;
         job.members_y = c->view.secondary;
     }
     job.requests = static_cast<const uint32_t*>(device_requests);

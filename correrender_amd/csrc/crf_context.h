@@ -54,7 +54,13 @@ struct crf_grid_state {
     crf_member_set members, narrow;
     int format = CRF_MEMBER_F32;
     crf::DeviceBuffer<float> wide;
-    crf_member_set secondary;  // second scalar field of the SEPARATE / SEPARATE_SYMMETRIC modes, optional, fp32
+    // The second scalar field of the SEPARATE / SEPARATE_SYMMETRIC modes, optional, held like the primary one: fp32 members
+    // in `secondary`, narrow ones in `secondary_narrow`, and then `secondary` empty until an evaluation without a native
+    // route needs fp32 values and points it into `secondary_wide` (api.cpp: ensure_secondary_wide).
+    crf_member_set secondary, secondary_narrow;
+    int secondary_format = CRF_MEMBER_F32;
+    crf::DeviceBuffer<float> secondary_wide;
+    bool has_secondary() const { return !(secondary_format == CRF_MEMBER_F32 ? secondary : secondary_narrow).ptrs.empty(); }
     // packed copy of fp32 members for the Pearson field (crf_internal.h), built at the first Pearson field evaluation
     // after the members change (api.cpp: ensure_packed)
     crf::DeviceBuffer<unsigned char> packed;  // header, then body
@@ -88,6 +94,7 @@ struct crf_launch_view {
     size_t num_voxels = 0;
     int max_vpt = 1;
     int scratch_set = 0;  // the crf_scratch the launch being issued writes
+    const void* const* secondary_narrow = nullptr;  // secondary members in their narrow format
 };
 
 // Members are destroyed in reverse order of declaration, and crf_destroy relies on it: `stream` comes first because it

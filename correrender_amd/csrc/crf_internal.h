@@ -6,7 +6,8 @@
 #include <cstdint>
 
 #include "../../include/corrfield.h"
-#include "two_vector_route.h"  // kMaxSortMembers, kMaxSymmetricRegisterMembers
+#include "symmetric_narrow_route.h"  // symmetric_narrow_routed
+#include "two_vector_route.h"        // kMaxSortMembers, kMaxSymmetricRegisterMembers
 
 namespace crf {
 
@@ -175,6 +176,13 @@ inline size_t member_format_bytes(int format) {
 hipError_t launch_pearson_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, bool out_vector,
                                  const RefSource& ref, float* d_prep, float* d_out, hipStream_t s, hipEvent_t ev_begin,
                                  hipEvent_t ev_end, LaunchInfo* info);
+// The symmetric Pearson field over two fields in one narrow format, read as stored (pearson_symmetric_narrow_kernel):
+// out[v] = Pearson(d_narrow_x[.][v], d_narrow_y[.][v]), bit-identical to launch_pearson_two_vector in field mode on the
+// converted values.  Both tables as d_narrow above (every pointer 4-byte aligned); symmetric_narrow_routed(format, cs)
+// must hold, else hipErrorInvalidValue.  Main kernel and tail kernel are bracketed by one event pair.
+hipError_t launch_pearson_symmetric_narrow(const void* const* d_narrow_x, const void* const* d_narrow_y, int format, int cs,
+                                           size_t num_voxels, bool out_vector, float* d_out, hipStream_t s,
+                                           hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 // member c of the fp32 copy = d_block + c * stride, num_voxels converted values each
 hipError_t launch_widen_members(const void* const* d_narrow, int format, int cs, size_t num_voxels, float* d_block,
                                 size_t stride, hipStream_t s);

@@ -607,10 +607,11 @@ int check_call(crf_group* g, const crf_params* params, int count, float* const* 
     }
     // the exchange reads another context's member table as fp32 (crf::RefOverride)
     for (int r = 0; r < g->n; r++)
-        if (g->slots[size_t(r)].ctx->grid.format != CRF_MEMBER_F32)
+        if (g->slots[size_t(r)].ctx->grid.format != CRF_MEMBER_F32 ||
+            g->slots[size_t(r)].ctx->grid.secondary_format != CRF_MEMBER_F32)
             return gfail(g, CRF_ERR_UNSUPPORTED,
                          fmt("device groups evaluate fp32 members only: the context of slot %d holds members in a narrow "
-                             "native format (crf_bind_members_device_format)", r));
+                             "native format (crf_bind_members_device_format, crf_bind_secondary_members_device_format)", r));
     return CRF_OK;
 }
 

@@ -360,16 +360,34 @@ void CorrelationCalculator::ensureMembersResident(int timeStepIdx, int ensembleI
 
 // SEPARATE_SYMMETRIC: the second field's members (fieldEntriesSecondary, CorrelationCalculator.cpp:1182-1216).  Uploaded
 // per evaluation: the mode is rare and a second residency cache would have to follow the primary one's invalidation.
+// Like the primary members (ensureMembersResident), entries that all share one narrow native format go to a single device
+// as they are stored -- no float view is converted on the host, half or a quarter of the bytes cross the bus per
+// evaluation; a device group, and entries of mixed formats, take the float views.
 void CorrelationCalculator::uploadSecondaryMembers(int timeStepIdx, int ensembleIdx, int cs) {
     const std::string& fieldName = scalarFieldNames.at(size_t(fieldIndex2Gui));
     std::vector<HostCacheEntry> fieldEntries;
-    std::vector<const float*> fields;
-    for (int fieldIdx = 0; fieldIdx < cs; fieldIdx++) {
+    fieldEntries.reserve(size_t(cs));
+    for (int fieldIdx = 0; fieldIdx < cs; fieldIdx++)
         fieldEntries.push_back(getFieldEntryCpu(fieldName, fieldIdx, timeStepIdx, ensembleIdx));
-        fields.push_back(fieldEntries.back()->data<float>());
+    const ScalarDataFormat native = fieldEntries[0]->getScalarDataFormatNative();
+    bool sameFormat = true;
+    for (const HostCacheEntry& entry : fieldEntries) sameFormat = sameFormat && entry->getScalarDataFormatNative() == native;
+    int format = CRF_MEMBER_F32;
+    if (!group && sameFormat && native != ScalarDataFormat::FLOAT)
+        format = native == ScalarDataFormat::BYTE ? CRF_MEMBER_U8 : native == ScalarDataFormat::SHORT ? CRF_MEMBER_U16 : CRF_MEMBER_F16;
+    if (format != CRF_MEMBER_F32) {
+        std::vector<const void*> natives;
+        natives.reserve(size_t(cs));
+        for (const HostCacheEntry& entry : fieldEntries) natives.push_back(entry->getDataNative());
+        if (crf_upload_secondary_members_format(ctx, format, natives.data())) throwBackendError("calculateCpu");
+    } else {
+        std::vector<const float*> fields;
+        fields.reserve(size_t(cs));
+        for (const HostCacheEntry& entry : fieldEntries) fields.push_back(entry->data<float>());
+        if (group ? crf_group_upload_secondary_members(group, fields.data()) : crf_upload_secondary_members(ctx, fields.data()))
+            throwBackendError("calculateCpu");
     }
-    if (group ? crf_group_upload_secondary_members(group, fields.data()) : crf_upload_secondary_members(ctx, fields.data()))
-        throwBackendError("calculateCpu");
+    residentSecondaryFormat = format;
 }
 
 void CorrelationCalculator::calculateCpu(int timeStepIdx, int ensembleIdx, float* buffer) {

@@ -99,6 +99,8 @@ public:
     /// crf_member_format of the members the last calculateCpu left resident on the device: a narrow format when every
     /// member entry shared it and one device evaluates, else CRF_MEMBER_F32.
     int getResidentMemberFormat() const { return residentFormat; }
+    /// ... and of the second field's members the last SEPARATE_SYMMETRIC evaluation uploaded (same rule).
+    int getResidentSecondaryMemberFormat() const { return residentSecondaryFormat; }
 
 protected:
     void onCorrelationMemberCountChanged() override;
@@ -120,6 +122,7 @@ private:
     int residentT = -1, residentE = -1, residentCs = -1;
     bool residentEnsembleMode = true;
     int residentFormat = CRF_MEMBER_F32;
+    int residentSecondaryFormat = CRF_MEMBER_F32;
     int cachedMemberCount = 0;
     CorrelationMeasureType correlationMeasureType = CorrelationMeasureType::MUTUAL_INFORMATION_KRASKOV;
     bool useGpu = true;   ///< "device" setting: "CPU" is accepted and remembered, evaluation always runs on the GPU.

@@ -952,6 +952,201 @@ __global__ __launch_bounds__(256, MIN_WAVES) void pearson_symmetric_kernel(const
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Symmetric field mode on two fields in ONE narrow native format: pearson_symmetric_kernel with both fields kept as they
+// are in memory, in the register scheme of pearson_narrow_kernel.  One lane owns the VPL voxels of one dword of every
+// member of both fields; all 2 cs raw-buffer dword loads are issued before the first use and the 2 cs raw dwords stay in
+// registers for the three passes (2 cs VGPRs for 2 or 4 voxels where the fp32 kernel needs 2 cs per voxel); each pass
+// converts on use, two voxels at a time in packed fp32, and the dwords are laundered between the passes so that the
+// compiler does not keep converted values.  2 cs e + 4 algorithmic bytes per voxel (e = element size).  The arithmetic
+// is pearson_symmetric_kernel's in its order; a skipped padded slot is the +0 that kernel adds for it in every pass (its
+// sums start at +0 and can never become -0).  The division branch is taken per wave as there, over VPL times the voxels:
+// exact_div equals the plain quotient wherever its guard holds, so which waves take which branch does not show.
+// `covered` as for pearson_narrow_kernel; launch_pearson_symmetric_narrow gives the rest to the tail kernel.
+// ---------------------------------------------------------------------------------------------------------
+template <int FMT, int CS_PAD, bool EXACT, int MIN_WAVES>
+__global__ __launch_bounds__(256, MIN_WAVES) void pearson_symmetric_narrow_kernel(
+    const void* const* __restrict__ members_x, const void* const* __restrict__ members_y, float* __restrict__ out,
+    uint32_t covered, int cs, int out_vector) {
+    constexpr int VPL = narrow_vpl<FMT>(), P = VPL / 2;  // voxels, and pairs of voxels, per lane
+    constexpr int kFirstGuarded = EXACT ? CS_PAD : CS_PAD - pad_granule(CS_PAD);
+    // a scheduling region is 2 pairs of voxels of each field: one slot (8-bit) or two (16-bit).  (Four slots, as in
+    // pearson_narrow_kernel, are 4 or 8 chains per field here, and the scheduler interleaves them all.)
+    constexpr int kBarrierMask = P == 2 ? 0 : 1;
+    int mine = cs;  // slot e is a member iff e < mine (laundered before each pass: see pearson_narrow_kernel)
+    const auto is_member = [&mine](int e) { return e < kFirstGuarded || e < mine; };
+    const uint32_t dword = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t v0 = dword * VPL;
+    const uint32_t byte_offset = dword * 4u;
+    const uint32_t bytes = covered / VPL * 4u;  // descriptor bound: lanes past the end read 0 and store nothing
+    uint32_t wx[CS_PAD], wy[CS_PAD];
+    // (unroll(full) on the slot loops: `#pragma unroll` gives up above a size that the 8-bit bodies reach at 112 slots, and a
+    // loop left rolled indexes wx / wy dynamically, which moves them to scratch)
+#pragma clang loop unroll(full)
+    for (int e = 0; e < CS_PAD; e++) {
+        wx[e] = wy[e] = 0u;
+        if (is_member(e)) {  // a uniform branch around each of the few guarded loads (they are the last loads issued)
+            const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(members_x[e]), short(0), int(bytes), 0x00020000);
+            const auto ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(members_y[e]), short(0), int(bytes), 0x00020000);
+            wx[e] = __builtin_amdgcn_raw_buffer_load_b32(rx, int(byte_offset), 0, kAuxNonTemporal);
+            wy[e] = __builtin_amdgcn_raw_buffer_load_b32(ry, int(byte_offset), 0, kAuxNonTemporal);
+        }
+    }
+    const float n = float(cs);
+    const float invN = 1.0f / n;
+    const float invNm1 = 1.0f / (n - 1.0f);
+    const f2 zero2 = {0.0f, 0.0f};
+    // Laundered before each pass as in pearson_narrow_kernel.  The sums of the pass that ends are pinned first, so that the
+    // pass is over before the first dword is laundered (a chain of it moved behind the launder would keep both
+    // generations of the dwords alive).
+    const auto launder = [&wx, &wy, &mine](f2 (&sum_x)[P], f2 (&sum_y)[P]) {
+#pragma unroll
+        for (int p = 0; p < P; p++) asm volatile("" : "+v"(sum_x[p]), "+v"(sum_y[p]));
+#pragma clang loop unroll(full)
+        for (int e = 0; e < CS_PAD; e++) {
+            asm volatile("" : "+v"(wx[e]));
+            asm volatile("" : "+v"(wy[e]));
+        }
+        asm volatile("" : "+s"(mine));
+    };
+    // pass 1: mean += invN * v_e
+    f2 meanX[P], meanY[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) meanX[p] = meanY[p] = zero2;
+    {
+        const f2 scale = {invN, invN};
+#pragma clang loop unroll(full)
+        for (int e = 0; e < CS_PAD; e++) {
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (!is_member(e)) continue;  // uniform
+                meanX[p] += scale * narrow_pair<FMT>(wx[e], p);
+                meanY[p] += scale * narrow_pair<FMT>(wy[e], p);
+            }
+            if ((e & kBarrierMask) == kBarrierMask) __builtin_amdgcn_sched_barrier(0);  // (else the conversions of many slots run ahead)
+        }
+    }
+    launder(meanX, meanY);
+    // pass 2: var += (invNm1 * d_e) * d_e, d_e = v_e - mean
+    f2 varX[P], varY[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) varX[p] = varY[p] = zero2;
+    {
+        const f2 scale = {invNm1, invNm1};
+#pragma clang loop unroll(full)
+        for (int e = 0; e < CS_PAD; e++) {
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                if (!is_member(e)) continue;  // uniform
+                const f2 dx = narrow_pair<FMT>(wx[e], p) - meanX[p];
+                const f2 dy = narrow_pair<FMT>(wy[e], p) - meanY[p];
+                varX[p] += (scale * dx) * dx;
+                varY[p] += (scale * dy) * dy;
+            }
+            if ((e & kBarrierMask) == kBarrierMask) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    launder(varX, varY);
+    f2 sdX[P], sdY[P], r[P];
+    int guard = 1;  // (no short circuit: nothing of a pass is to be sunk behind a branch)
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        sdX[p] = f2{sqrtf(varX[p][0]), sqrtf(varX[p][1])};
+        sdY[p] = f2{sqrtf(varY[p][0]), sqrtf(varY[p][1])};
+        r[p] = zero2;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+            guard &= int(exact_div_guard(meanX[p][i], sdX[p][i])) & int(exact_div_guard(meanY[p][i], sdY[p][i]));
+    }
+    // pass 3: r += (invNm1 * (dx_e / sdX)) * (dy_e / sdY).  The choice between the exact quotients through one reciprocal per
+    // voxel and side (crf_exact_div.h: exact_div) and the plain divisions (a constant voxel, sd = 0, or a tiny mean somewhere
+    // in the wave) is a uniform branch inside every slot, behind the conversions: written as two loops, both begin with the
+    // same conversions, the compiler hoists them above the branch, all of them at once, and the kernel is back at the
+    // fp32 kernel's footprint.  (The flag is laundered per slot so that the branches are not threaded into two loops again.)
+    int exact = __builtin_amdgcn_readfirstlane(__all(guard) ? 1 : 0);
+    f2 rcpX[P], rcpY[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        rcpX[p] = f2{1.0f / sdX[p][0], 1.0f / sdX[p][1]};
+        rcpY[p] = f2{1.0f / sdY[p][0], 1.0f / sdY[p][1]};
+    }
+    const f2 scale3 = {invNm1, invNm1};
+#pragma clang loop unroll(full)
+    for (int e = 0; e < CS_PAD; e++) {
+        if (!is_member(e)) continue;  // uniform
+        f2 dx[P], dy[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            dx[p] = narrow_pair<FMT>(wx[e], p) - meanX[p];
+            dy[p] = narrow_pair<FMT>(wy[e], p) - meanY[p];
+        }
+        asm volatile("" : "+s"(exact));
+        if (exact) {
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                const f2 qx0 = dx[p] * rcpX[p], qy0 = dy[p] * rcpY[p];
+                const f2 remx = __builtin_elementwise_fma(-qx0, sdX[p], dx[p]);
+                const f2 remy = __builtin_elementwise_fma(-qy0, sdY[p], dy[p]);
+                const f2 qx = __builtin_elementwise_fma(remx, rcpX[p], qx0);
+                const f2 qy = __builtin_elementwise_fma(remy, rcpY[p], qy0);
+                r[p] += (scale3 * qx) * qy;
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < P; p++)
+#pragma unroll
+                for (int i = 0; i < 2; i++) r[p][i] += (invNm1 * (dx[p][i] / sdX[p][i])) * (dy[p][i] / sdY[p][i]);
+        }
+        // (pinned per slot: the additions are common to both arms, and left alone the compiler moves them all behind the last
+        // slot and keeps every slot's products until then)
+#pragma unroll
+        for (int p = 0; p < P; p++) asm volatile("" : "+v"(r[p]));
+    }
+    if (v0 + VPL <= covered) {
+        if (out_vector) {
+            typedef float fv __attribute__((ext_vector_type(VPL)));
+            fv v;
+#pragma unroll
+            for (int i = 0; i < VPL; i++) v[i] = r[i / 2][i % 2];
+            __builtin_nontemporal_store(v, reinterpret_cast<fv*>(out + v0));
+        } else {
+#pragma unroll
+            for (int i = 0; i < VPL; i++) store_result_nt(out + v0 + i, r[i / 2][i % 2]);
+        }
+    }
+}
+
+// the up to VPL - 1 voxels behind the last whole dword of the two narrow fields: one voxel per lane, three passes
+template <int FMT>
+__global__ __launch_bounds__(64) void pearson_symmetric_narrow_tail_kernel(const void* const* __restrict__ members_x,
+                                                                           const void* const* __restrict__ members_y,
+                                                                           float* __restrict__ out, size_t voxel_offset,
+                                                                           size_t voxel_end, int cs) {
+    const size_t v0 = voxel_offset + size_t(blockIdx.x) * 64 + threadIdx.x;
+    if (v0 >= voxel_end) return;
+    const float n = float(cs);
+    const float invN = 1.0f / n;
+    const float invNm1 = 1.0f / (n - 1.0f);
+    float meanX = 0.0f, meanY = 0.0f;
+    for (int e = 0; e < cs; e++) {
+        meanX += invN * narrow_value<FMT>(members_x[e], v0);
+        meanY += invN * narrow_value<FMT>(members_y[e], v0);
+    }
+    float varX = 0.0f, varY = 0.0f;
+    for (int e = 0; e < cs; e++) {
+        const float dx = narrow_value<FMT>(members_x[e], v0) - meanX;
+        const float dy = narrow_value<FMT>(members_y[e], v0) - meanY;
+        varX += invNm1 * dx * dx;
+        varY += invNm1 * dy * dy;
+    }
+    const float sdX = sqrtf(varX), sdY = sqrtf(varY);
+    float r = 0.0f;
+    for (int e = 0; e < cs; e++)
+        r += (invNm1 * ((narrow_value<FMT>(members_x[e], v0) - meanX) / sdX)) *
+             ((narrow_value<FMT>(members_y[e], v0) - meanY) / sdY);
+    store_result_nt(out + v0, r);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Streaming fallback for any cs (three passes re-reading the members; the second and third mostly hit L2/MALL) and
 // for the ragged tail of the grid.  One voxel per lane, bounds-checked.
 // ---------------------------------------------------------------------------------------------------------
@@ -1269,6 +1464,75 @@ hipError_t launch_pearson_narrow(const void* const* d_narrow, int format, int cs
         default: return hipErrorInvalidValue;
     }
     if (info) info->kernel_name = "pearson_narrow_kernel";
+    if (ev_end) (void)hipEventRecord(ev_end, s);
+    return hipGetLastError();
+}
+
+namespace {
+// occupancy request of pearson_symmetric_narrow_kernel.  Registers: 2 x CS_PAD raw dwords + the working set of one pair
+// of voxels (16-bit formats) or two (8-bit) of both fields; each instantiation at the most waves per SIMD it reaches
+// without scratch (tools/resource_usage.py; the table is in profiles/narrow_symmetric_ab.md).
+constexpr int symmetric_narrow_min_waves(int format, int cs_pad, bool exact) {
+    if (format == CRF_MEMBER_U8)
+        return cs_pad == 8 ? (exact ? 8 : 6) : cs_pad == 16 ? 6 : cs_pad == 32 ? 4 : cs_pad == 48 ? 3 : cs_pad <= 96 ? 2 : 1;
+    return cs_pad <= 16 ? 8 : cs_pad == 32 ? 5 : cs_pad == 48 ? 4 : cs_pad == 64 ? 3 : cs_pad <= 112 ? 2 : 1;
+}
+
+template <int FMT, int CS_PAD>
+void launch_symmetric_narrow(const void* const* d_x, const void* const* d_y, float* d_out, size_t covered, int cs,
+                             bool out_vector, hipStream_t s) {
+    const size_t per_block = size_t(256) * narrow_vpl<FMT>();
+    const dim3 grid(unsigned((covered + per_block - 1) / per_block)), block(256);
+    if (cs == CS_PAD)
+        hipLaunchKernelGGL((pearson_symmetric_narrow_kernel<FMT, CS_PAD, true, symmetric_narrow_min_waves(FMT, CS_PAD, true)>),
+                           grid, block, 0, s, d_x, d_y, d_out, uint32_t(covered), cs, out_vector ? 1 : 0);
+    else
+        hipLaunchKernelGGL((pearson_symmetric_narrow_kernel<FMT, CS_PAD, false, symmetric_narrow_min_waves(FMT, CS_PAD, false)>),
+                           grid, block, 0, s, d_x, d_y, d_out, uint32_t(covered), cs, out_vector ? 1 : 0);
+}
+
+template <int FMT>
+void launch_symmetric_narrow_format(const void* const* d_x, const void* const* d_y, float* d_out, size_t num_voxels, int cs,
+                                    bool out_vector, hipStream_t s) {
+    const size_t covered = num_voxels / narrow_vpl<FMT>() * narrow_vpl<FMT>();
+    if (covered > 0) {
+        switch (cs <= 8 ? 8 : (cs + 15) / 16 * 16) {
+            case 8: launch_symmetric_narrow<FMT, 8>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            case 16: launch_symmetric_narrow<FMT, 16>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            case 32: launch_symmetric_narrow<FMT, 32>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            case 48: launch_symmetric_narrow<FMT, 48>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            case 64: launch_symmetric_narrow<FMT, 64>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            case 80: launch_symmetric_narrow<FMT, 80>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            case 96: launch_symmetric_narrow<FMT, 96>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            case 112: launch_symmetric_narrow<FMT, 112>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+            default: launch_symmetric_narrow<FMT, 128>(d_x, d_y, d_out, covered, cs, out_vector, s); break;
+        }
+    }
+    if (covered < num_voxels)
+        hipLaunchKernelGGL(pearson_symmetric_narrow_tail_kernel<FMT>, dim3(1), dim3(64), 0, s, d_x, d_y, d_out, covered,
+                           num_voxels, cs);
+}
+}  // namespace
+
+hipError_t launch_pearson_symmetric_narrow(const void* const* d_narrow_x, const void* const* d_narrow_y, int format, int cs,
+                                           size_t num_voxels, bool out_vector, float* d_out, hipStream_t s,
+                                           hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    if (!symmetric_narrow_routed(format, cs) || !d_narrow_x || !d_narrow_y || !d_out ||
+        num_voxels * member_format_bytes(format) >= kNarrowMaxBytes)
+        return hipErrorInvalidValue;
+    if (ev_begin) (void)hipEventRecord(ev_begin, s);
+    switch (format) {
+        case CRF_MEMBER_U8:
+            launch_symmetric_narrow_format<CRF_MEMBER_U8>(d_narrow_x, d_narrow_y, d_out, num_voxels, cs, out_vector, s);
+            break;
+        case CRF_MEMBER_U16:
+            launch_symmetric_narrow_format<CRF_MEMBER_U16>(d_narrow_x, d_narrow_y, d_out, num_voxels, cs, out_vector, s);
+            break;
+        default:
+            launch_symmetric_narrow_format<CRF_MEMBER_F16>(d_narrow_x, d_narrow_y, d_out, num_voxels, cs, out_vector, s);
+            break;
+    }
+    if (info) info->kernel_name = "pearson_symmetric_narrow_kernel";
     if (ev_end) (void)hipEventRecord(ev_end, s);
     return hipGetLastError();
 }

@@ -188,20 +188,48 @@ class CorrField:
 
     # -- secondary members: the second scalar field of the SEPARATE / SEPARATE_SYMMETRIC field modes ---------
     def upload_secondary_members(self, members: Sequence[np.ndarray]):
-        arrs = [np.ascontiguousarray(m, dtype=np.float32) for m in members]
+        """The second field, with upload_members' rule for dtypes: arrays that are all float16, uint16 or uint8 stay in
+        that format on the device (value = float(h), s / 65535, b / 255); anything else is cast to float32 by value."""
+        dtypes = {np.asarray(m).dtype for m in members}
+        narrow = len(dtypes) == 1 and next(iter(dtypes)) in (np.dtype(np.float16), np.dtype(np.uint16), np.dtype(np.uint8))
+        dtype = next(iter(dtypes)) if narrow else np.dtype(np.float32)
+        arrs = [np.ascontiguousarray(m, dtype=dtype) for m in members]
         if len(arrs) != self.cs or any(a.size != self.num_voxels for a in arrs):
             raise ValueError("secondary members do not match the grid declared with set_grid")
         ptrs = (C.c_void_p * self.cs)(*[a.ctypes.data for a in arrs])
-        self._check(self._lib.crf_upload_secondary_members(self._ctx, ptrs))
+        if narrow:
+            self._check(self._lib.crf_upload_secondary_members_format(self._ctx, _member_format(dtype), ptrs))
+        else:
+            self._check(self._lib.crf_upload_secondary_members(self._ctx, ptrs))
 
     def bind_secondary_members(self, members):
+        """cs torch CUDA tensors, borrowed; the dtype decides the format as for bind_members (any other raises TypeError).
+        The symmetric Pearson field at 2..128 members reads two fields of the same narrow format as stored when every
+        member of both starts on a 4-byte boundary and the grid is not windowed (last_member_format() names the format);
+        secondary_member_minmax and reference_from_secondary read narrow secondary members as stored at any alignment;
+        every other evaluation that reads them runs on an fp32 copy (secondary_wide_copy_bytes())."""
         tensors = [members[i] for i in range(self.cs)]
+        formats = {_member_format(t.dtype) for t in tensors}
+        if len(formats) != 1:
+            raise TypeError("every secondary member must have the same dtype")
+        fmt = formats.pop()
         for t in tensors:
-            if not t.is_cuda or not t.is_contiguous() or t.numel() != self.num_voxels or t.element_size() != 4:
-                raise ValueError("each member must be a contiguous CUDA float32 tensor of xs*ys*zs elements")
+            if not t.is_cuda or not t.is_contiguous() or t.numel() != self.num_voxels:
+                raise ValueError("each member must be a contiguous CUDA tensor of xs*ys*zs elements")
         ptrs = (C.c_void_p * self.cs)(*[t.data_ptr() for t in tensors])
-        self._check(self._lib.crf_bind_secondary_members_device(self._ctx, ptrs))
+        if fmt == 0:
+            self._check(self._lib.crf_bind_secondary_members_device(self._ctx, ptrs))
+        else:
+            self._check(self._lib.crf_bind_secondary_members_device_format(self._ctx, fmt, ptrs))
         self._keepalive_secondary = (members, tensors)
+
+    def secondary_member_format(self) -> str:
+        """"f32", "u8", "u16" or "f16": the format of the bound secondary members."""
+        return MEMBER_FORMATS[self._lib.crf_secondary_member_format(self._ctx)]
+
+    def secondary_wide_copy_bytes(self) -> int:
+        """Bytes of the fp32 copy of narrow secondary members that the context holds right now (0: none)."""
+        return int(self._lib.crf_secondary_wide_copy_bytes(self._ctx))
 
     def secondary_member_minmax(self):
         mn, mx = C.c_float(), C.c_float()

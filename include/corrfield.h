@@ -128,7 +128,9 @@ const char* crf_last_error(const crf_context* ctx);
 /* ABI version of this header, bumped on incompatible change. */
 int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_minmax_divergent; added since, compatibly:
                                   crf_upload_members_format, crf_bind_members_device_format, crf_member_format,
-                                  crf_last_member_format, crf_wide_copy_bytes, crf_window_count;
+                                  crf_last_member_format, crf_wide_copy_bytes, crf_window_count,
+                                  crf_upload_secondary_members_format, crf_bind_secondary_members_device_format,
+                                  crf_secondary_member_format, crf_secondary_wide_copy_bytes;
                                4: crf_group_* (several devices behind one caller thread), crf_set_kraskov_noise;
                                3: crf_params.reserved[0] became prepared_slot (same layout; 0 keeps the old meaning) */
 
@@ -146,7 +148,7 @@ int crf_window_count(const crf_context* ctx);
 int crf_upload_members(crf_context* ctx, const float* const* host_members);
 /* Uses cs caller-owned DEVICE volumes in place (borrowed until the next set_grid/upload/bind/destroy). */
 int crf_bind_members_device(crf_context* ctx, const void* const* device_members);
-/* ---- primary members in a narrow native format -------------------------------------------------------------------
+/* ---- members in a narrow native format ---------------------------------------------------------------------------
  * The reference keeps scalar fields as float, unsigned byte, unsigned short or float16 (format_cast,
  * src/Loaders/DataSetList.cpp:185-195) and its calculators see them through HostCacheEntry::data<float>()
  * (src/Volume/Cache/HostCacheEntry.cpp:107-176); the value of an element is given below.  Members in such a format
@@ -198,7 +200,8 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *     native call as they move an fp32 call.  Like the other sibling reductions it leaves crf_last_member_format alone.
  *   - crf_member_minmax and the reference gathers (crf_gather_reference, crf_gather_reference_device,
  *     crf_gather_reference_rows_device) read the narrow members directly, whatever their alignment.
- *   - Everything else -- Spearman at 2..32 members, symmetric and pair-request evaluations, and the
+ *   - Everything else -- Spearman at 2..32 members, symmetric evaluations (but for the Pearson field over two narrow fields
+ *     described with the secondary members below) and pair-request evaluations, and the
  *     Pearson, Spearman, Kendall, binned-MI and Kraskov-MI fields above 128 members (binned MI, Kraskov MI and DKL also at
  *     the counts named above) -- runs on an fp32 copy of the members that the context builds on the compute stream at the first
  *     call that needs it (one owned block of cs x xs*ys*zs floats; CRF_ERR_DEVICE naming the copy and its size if it
@@ -206,10 +209,27 @@ int crf_bind_members_device(crf_context* ctx, const void* const* device_members)
  *     returns CRF_MEMBER_F32.  So do the Pearson field and the sibling reductions over borrowed members that are not all
  *     4-byte aligned.  A context that only runs the entry points of the eight items above never builds the copy;
  *     crf_wide_copy_bytes tells.
- *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.  Secondary members are fp32 only.
- *     crf_group_* evaluations on a context that holds narrow members: CRF_ERR_UNSUPPORTED.
- * format == CRF_MEMBER_F32 behaves exactly like crf_upload_members / crf_bind_members_device, which set the format to
- * CRF_MEMBER_F32. */
+ *   - A local grid whose narrow member is 4 GiB or more: CRF_ERR_UNSUPPORTED.
+ *     crf_group_* evaluations on a context that holds narrow members, primary or secondary: CRF_ERR_UNSUPPORTED.
+ * Secondary members (crf_upload_secondary_members_format, crf_bind_secondary_members_device_format) stay as narrow in HBM
+ * too, and every entry point that reads them gives exactly the result of the same call on fp32 secondary members that
+ * hold those values:
+ *   - crf_secondary_member_minmax, crf_member_minmax_divergent(secondary = 1) and the reference vector of
+ *     CRF_FLAG_REFERENCE_FROM_SECONDARY read them directly, whatever their alignment; the rest of such an evaluation is
+ *     that of the primary members (their native routes included).
+ *   - The symmetric Pearson field (CRF_PEARSON with CRF_FLAG_SYMMETRIC) at 2..128 members reads BOTH fields directly when
+ *     they are in the same narrow format, all members of both are 4-byte aligned and the grid is not windowed
+ *     (pearson_symmetric_narrow_kernel, reported by crf_last_kernel_name: one lane owns the voxels of one dword, 2 cs e + 4
+ *     bytes per voxel for elements of e bytes where the fp32 kernel moves 8 cs + 4); crf_last_member_format then returns
+ *     the narrow format and neither fp32 copy is built.
+ *   - Every other reader -- the symmetric mode for the other measures, for fields in different formats, for borrowed
+ *     members that are not all 4-byte aligned, above 128 members and on windowed grids; pair requests with
+ *     CRF_FLAG_QUERY_FROM_SECONDARY -- takes fp32 views: of the secondary members through an fp32 copy of their own (built
+ *     at the first call that needs it, dropped by crf_set_grid, a secondary upload or bind and crf_members_changed;
+ *     crf_secondary_wide_copy_bytes tells), of narrow primary members through theirs.  crf_last_member_format then
+ *     returns CRF_MEMBER_F32.
+ * format == CRF_MEMBER_F32 behaves exactly like crf_upload_members / crf_bind_members_device (and their secondary
+ * counterparts), which set the format to CRF_MEMBER_F32.  An unknown format: CRF_ERR_ARGUMENT. */
 enum crf_member_format { /* a tag only: the function crf_member_format() below shares the name */
     CRF_MEMBER_F32 = 0,
     CRF_MEMBER_U8 = 1,   /* value = float(b) / 255.0f */
@@ -242,6 +262,12 @@ int crf_member_minmax_divergent(crf_context* ctx, int secondary, float* out_min,
 int crf_upload_secondary_members(crf_context* ctx, const float* const* host_members);
 int crf_bind_secondary_members_device(crf_context* ctx, const void* const* device_members);
 int crf_secondary_member_minmax(crf_context* ctx, float* out_min, float* out_max);
+/* ... in a narrow native format (see "members in a narrow native format" above) */
+int crf_upload_secondary_members_format(crf_context* ctx, int format, const void* const* host_members);
+int crf_bind_secondary_members_device_format(crf_context* ctx, int format, const void* const* device_members);
+int crf_secondary_member_format(const crf_context* ctx);      /* format of the bound secondary members */
+/* bytes of the fp32 copy of narrow secondary members held right now; 0 if none or ctx == NULL */
+size_t crf_secondary_wide_copy_bytes(const crf_context* ctx);
 
 /* ---- reference vector (CorrelationCalculator.cpp:802,815-817) --------------------------------------------- */
 /* referenceValues[c] = member_c[IDXS(x,y,z)] -> cs floats to a host buffer (synchronous) ... */
