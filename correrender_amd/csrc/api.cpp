@@ -29,6 +29,7 @@
 #include "crf_context.h"
 #include "crf_host_copy.h"
 #include "crf_internal.h"
+#include "crf_similarity_tail.h"
 
 namespace {
 thread_local std::string g_create_error;
@@ -1573,6 +1574,69 @@ int crf_compute_dkl_device(crf_context* c, int estimator, int num_bins, int k, v
 
 int crf_compute_dkl(crf_context* c, int estimator, int num_bins, int k, float* host_out) {
     return to_host(c, host_out, [&](void* d) { return crf_compute_dkl_device(c, estimator, num_bins, k, d, nullptr); });
+}
+
+// ---- whole-field similarity of the primary and the secondary field -----------------------------------------------------
+// computeFieldSimilarity<double> (Similarity.cpp:36-180) on two resident fields: Pearson in two streaming passes on the
+// device, the binned measures as a joint histogram on the device and the reference's own arithmetic from the integer
+// counts on the host (crf_similarity_tail.h).  Narrow members are read through their fp32 copies.
+int crf_field_similarity(crf_context* c, int measure, int member, int num_bins, float min_x, float max_x, float min_y,
+                         float max_y, float* out_value, unsigned long long* out_samples) {
+    if (int r = check_ready(c)) return r;
+    if (!out_value) return fail(c, CRF_ERR_ARGUMENT, "null output");
+    if (!c->grid.has_secondary())
+        return fail(c, CRF_ERR_STATE, "crf_field_similarity needs secondary members (crf_upload_secondary_members)");
+    if (measure < CRF_PEARSON || measure > CRF_KMI_CC) return fail(c, CRF_ERR_ARGUMENT, fmt("unknown measure %d", measure));
+    const bool binned = measure == CRF_MI_BINNED || measure == CRF_BINNED_MI_CC;
+    if (measure != CRF_PEARSON && !binned)
+        return fail(c, CRF_ERR_UNSUPPORTED,
+                    fmt("crf_field_similarity: measure %d needs a global sort (Spearman, Kendall) or a k-nearest-neighbour search "
+                        "(Kraskov MI) over all samples of the two fields, which is not implemented; Pearson and binned MI are",
+                        measure));
+    if (member < -1 || member >= c->cs)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("member %d outside [-1, %d)", member, c->cs));
+    if (binned && (num_bins < 1 || num_bins > crf::kSimilarityMaxBins))
+        return fail(c, CRF_ERR_ARGUMENT, fmt("num_bins %d outside [1,%d]", num_bins, crf::kSimilarityMaxBins));
+    if (c->windowed)
+        return fail(c, CRF_ERR_UNSUPPORTED, "crf_field_similarity does not evaluate windowed grids (member volumes of 4 GiB or more)");
+    const int members = member < 0 ? c->cs : 1;
+    if (size_t(members) * c->alloc_voxels > size_t(0x7FFFFFFF))
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%zu samples: the reference counts the samples of a field similarity in an int "
+                                                "(at most 2147483647)", size_t(members) * c->alloc_voxels));
+    if (int r = bind_device(c)) return r;
+    hipStream_t s = c->stream;
+    if (int r = ensure_wide(c, s)) return r;
+    if (int r = ensure_secondary_wide(c, s)) return r;
+    if (int r = ensure_workspace(c, crf::similarity_workspace_bytes())) return r;
+    const crf_grid_state& g = c->grid;
+    const int first = member < 0 ? 0 : member;
+    crf::SimilarityJob job{c->view.members + first, c->view.secondary + first, members, c->alloc_voxels,
+                           g.members.vpt == 4 && g.secondary.vpt == 4, g.scratch[0].workspace.get()};
+    TimedLaunch launch(c);
+    float value = 0.0f;
+    unsigned long long samples = 0;
+    if (!binned) {
+        if (int r = launch.finish(crf::launch_similarity_moments(job, s, launch.e0, launch.e1, &launch.info))) return r;
+        double stats[7];
+        CRF_HIP(c, hipMemcpyAsync(stats, crf::similarity_stats(job.workspace), sizeof stats, hipMemcpyDeviceToHost, s));
+        CRF_HIP(c, hipStreamSynchronize(s));
+        samples = (unsigned long long)stats[0];
+        value = float(stats[6]);
+    } else {
+        if (int r = launch.finish(crf::launch_similarity_histogram(job, num_bins, min_x, max_x, min_y, max_y, s, launch.e0,
+                                                                   launch.e1, &launch.info)))
+            return r;
+        std::vector<uint64_t> counts(size_t(num_bins) * size_t(num_bins));
+        CRF_HIP(c, hipMemcpyAsync(counts.data(), crf::similarity_histogram(job.workspace), counts.size() * sizeof(uint64_t),
+                                  hipMemcpyDeviceToHost, s));
+        CRF_HIP(c, hipMemcpyAsync(&samples, crf::similarity_samples(job.workspace), sizeof samples, hipMemcpyDeviceToHost, s));
+        CRF_HIP(c, hipStreamSynchronize(s));
+        value = crf::similarity_mi_from_counts(counts.data(), num_bins, samples);
+        if (measure == CRF_BINNED_MI_CC) value = crf::similarity_mi_to_cc(value);
+    }
+    *out_value = value;
+    if (out_samples) *out_samples = samples;
+    return CRF_OK;
 }
 
 // ---- helpers, instrumentation, synthetic data -------------------------------------------------------------------------

@@ -363,6 +363,37 @@ hipError_t launch_dkl_narrow(const void* const* d_narrow, int format, int cs, si
                              int k, double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s,
                              hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info);
 
+// ---- kernels_similarity.hip: whole-field similarity of two fields (crf_field_similarity) ------------------------------
+// ONE value over the samples (x[m][v], y[m][v]), m < members, v < num_voxels; a pair with a NaN on either side is left
+// out.  x, y: device tables of `members` fp32 volumes; num_voxels below 2^30 and members x num_voxels at most 2^31 - 1
+// (the reference counts samples in an int), else hipErrorInvalidValue.  vec16: every member of both tables is 16-byte
+// aligned (16-byte loads; dword loads otherwise, same bits).  workspace: similarity_workspace_bytes() of device memory,
+// 8-byte aligned, which also receives the results; both launchers are stream-ordered and leave reading them to the caller.
+constexpr int kSimilarityMaxBins = 128;  // num_bins^2 32-bit counters in 64 KiB of LDS
+struct SimilarityJob {
+    const float* const* x;
+    const float* const* y;
+    int members;
+    size_t num_voxels;
+    bool vec16;
+    unsigned char* workspace;
+};
+size_t similarity_workspace_bytes();
+// where the launchers leave their results inside the workspace
+const double* similarity_stats(const unsigned char* workspace);  // 7 doubles: N, mean x, mean y, Sxx, Syy, Sxy, value
+const unsigned long long* similarity_samples(const unsigned char* workspace);    // pairs without a NaN
+const unsigned long long* similarity_histogram(const unsigned char* workspace);  // num_bins^2 counts, x bin major
+// Pearson: two passes of similarity_moments_kernel, each followed by the one-block similarity_finish_kernel; no
+// floating-point atomics.  One event pair around the four launches.
+hipError_t launch_similarity_moments(const SimilarityJob& job, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
+                                     LaunchInfo* info);
+// The joint histogram of binned MI over x01 = (x - min_x) / (max_x - min_x), y01 likewise, formed in fp32, bin =
+// clamp(int(double(x01) * num_bins), 0, num_bins - 1) as compiled for x86-64 (crf_binned_bins.h).  1 <= num_bins <=
+// kSimilarityMaxBins.  The counts-to-MI tail runs on the host (crf_similarity_tail.h).
+hipError_t launch_similarity_histogram(const SimilarityJob& job, int num_bins, float min_x, float max_x, float min_y,
+                                       float max_y, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
+                                       LaunchInfo* info);
+
 // ---- two vectors per item: the symmetric field mode and pair requests --------------------------------------------------
 // One evaluation of a measure between two member vectors per item.  Field mode (requests == nullptr): item v is voxel
 // pair (v, v), X = members_x[.][v] (the primary field), Y = members_y[.][v] (the secondary field).  Request mode: item r

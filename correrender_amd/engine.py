@@ -457,6 +457,20 @@ class CorrField:
                                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
 
+    def field_similarity(self, measure, *, member: Optional[int] = None, num_bins: int = 80, minmax_x=(0.0, 1.0),
+                         minmax_y=(0.0, 1.0), return_samples: bool = False):
+        """computeFieldSimilarity<double> (src/Calculators/Similarity.cpp:36-180) between the primary field (x) and the
+        secondary field (y): ONE value of `measure` (Pearson or a binned-MI measure) over every voxel of every member,
+        or of member `member` alone; pairs with a NaN on either side are left out.  The binned measures normalise x with
+        `minmax_x` and y with `minmax_y`: (0, 1) twice is the reference's call verbatim, the fields' extrema
+        (member_minmax(), secondary_member_minmax()) give a meaningful number.  Returns the value, or (value, number of
+        pairs kept) with `return_samples`."""
+        value, samples = C.c_float(), C.c_ulonglong()
+        self._check(self._lib.crf_field_similarity(
+            self._ctx, int(measure), -1 if member is None else int(member), int(num_bins), C.c_float(minmax_x[0]),
+            C.c_float(minmax_x[1]), C.c_float(minmax_y[0]), C.c_float(minmax_y[1]), C.byref(value), C.byref(samples)))
+        return (value.value, int(samples.value)) if return_samples else value.value
+
     def tiled_element_count(self) -> int:
         return int(self._lib.crf_tiled_element_count(*self.grid))
 

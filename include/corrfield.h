@@ -130,7 +130,7 @@ int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_m
                                   crf_upload_members_format, crf_bind_members_device_format, crf_member_format,
                                   crf_last_member_format, crf_wide_copy_bytes, crf_window_count,
                                   crf_upload_secondary_members_format, crf_bind_secondary_members_device_format,
-                                  crf_secondary_member_format, crf_secondary_wide_copy_bytes;
+                                  crf_secondary_member_format, crf_secondary_wide_copy_bytes, crf_field_similarity;
                                4: crf_group_* (several devices behind one caller thread), crf_set_kraskov_noise;
                                3: crf_params.reserved[0] became prepared_slot (same layout; 0 keeps the old meaning) */
 
@@ -425,6 +425,45 @@ int crf_compute_set_predicate_device(crf_context* ctx, int comparison_operator, 
 typedef enum crf_dkl_estimator { CRF_DKL_BINNED = 0, CRF_DKL_ENTROPY_KNN = 1 } crf_dkl_estimator;
 int crf_compute_dkl(crf_context* ctx, int estimator, int num_bins, int k, float* host_out);
 int crf_compute_dkl_device(crf_context* ctx, int estimator, int num_bins, int k, void* device_out, void* stream);
+
+/* ---- whole-field similarity of two fields ------------------------------------------------------------------------------
+ * Whole-field similarity (src/Calculators/Similarity.cpp:36-180, the <double> instantiation): one value of `measure`
+ * over the samples (primary[c][v], secondary[c][v]) -- every voxel v of every member c (member == -1) or of member
+ * `member` alone; a pair with a NaN on either side is left out.  *out_samples = the number of pairs kept.
+ * It backs the reference's "Field Similarity" dialog (MainApp.cpp:1608-1618) and every cell of its correlation-matrix
+ * chart (CorrelationMatrixRenderer.cpp:91-101); INTEGRATION.md maps useAllTimeSteps / useAllEnsembleMembers onto it.
+ * Synchronous on the context's own stream; both fields stay where they are in HBM.
+ *   CRF_PEARSON        computePearsonParallel<double> (Correlation.cpp:182-268): means, then centred second moments, all
+ *                      accumulated in fp64, the result cast to float; here Sxy / (sqrt(Sxx) sqrt(Syy)) from two streaming
+ *                      passes (similarity_moments_kernel).  The reference sums under an OpenMP reduction, so bit identity
+ *                      with it is not defined; this library's value is bitwise reproducible from call to call (fixed
+ *                      summation order, no floating-point atomics) and the same for 16-byte-aligned and merely 4-byte-
+ *                      aligned borrowed members.  No pair kept: 0; one pair, or a constant side: NaN (a constant side
+ *                      centres to exactly 0 while N x value is exact in fp64: up to 2^29 samples at least).
+ *   CRF_MI_BINNED      computeMutualInformationBinned<double> (MutualInformation.cpp:45-143) on x01 = (x - min_x) /
+ *                      (max_x - min_x), y01 likewise, formed in IEEE fp32; bin = clamp(int(double(x01) * num_bins), 0,
+ *                      num_bins - 1) as the x86-64 build converts it (an out-of-range product lands in bin 0).  Ranges
+ *                      (0, 1, 0, 1) are the reference's call verbatim (Similarity.cpp:163 passes raw values; it fixes 80
+ *                      bins); the fields' extrema (crf_member_minmax, crf_secondary_member_minmax) give a meaningful
+ *                      number.  The joint histogram (similarity_histogram_kernel) holds integer counts, so it does not
+ *                      depend on the order of accumulation; everything after the counts is the reference's arithmetic in
+ *                      the reference's loop order, in fp64 with the host's log.  num_bins in [1, 128] (read by the binned
+ *                      measures only).
+ *                      ONE DELIBERATE DEVIATION: the reference forms EPSILON_2D = 0.5 / Real(es * es) with an int product
+ *                      (MutualInformation.cpp:121) that overflows from 46 341 samples on -- its object code returns NaN at
+ *                      46 341 samples and H(x) + H(y), the joint term dropped, at 65 536, 262 144 and 2^20.  This library
+ *                      forms the product in fp64: bit-identical to the object code up to 46 340 samples, well defined beyond.
+ *   CRF_BINNED_MI_CC   sqrt(1 - exp(-2 MI)) of that float (Similarity.cpp:165-167).
+ *   CRF_SPEARMAN, CRF_KENDALL, CRF_MI_KRASKOV, CRF_KMI_CC: CRF_ERR_UNSUPPORTED -- they need a global sort or a k-nearest-
+ *                      neighbour search over all N samples.
+ * Refusals (the context stays usable): no secondary members CRF_ERR_STATE; member outside [-1, cs) or num_bins outside
+ * [1, 128] CRF_ERR_ARGUMENT; a windowed grid (crf_window_count > 1), or more than 2^31 - 1 candidate samples (the
+ * reference counts samples in an int), CRF_ERR_UNSUPPORTED.  Members in a narrow format are read through their fp32
+ * copies (crf_wide_copy_bytes, crf_secondary_wide_copy_bytes).  crf_last_kernel_name reports similarity_moments_kernel or
+ * similarity_histogram_kernel; crf_set_profiling covers the call's launches with one event pair. */
+int crf_field_similarity(crf_context* ctx, int measure, int member, int num_bins,
+                         float min_x, float max_x, float min_y, float max_y,
+                         float* out_value, unsigned long long* out_samples /* may be NULL */);
 
 /* ---- result layout for the renderer -------------------------------------------------------------------------------- */
 /* The reference keeps device fields in 8x8x4 tiles (bufferTileSize, VolumeData.cpp:1581-1621; addressed by IDXS of
