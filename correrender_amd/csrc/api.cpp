@@ -499,6 +499,18 @@ int ensure_workspace(crf_context* c, size_t need) {
     return CRF_OK;
 }
 
+// The buffer of the device-wide sort (crf_context.h: rank_scratch).  Only synchronous calls on the context's own stream
+// use it, so nothing can still be reading an old one.
+int ensure_rank_scratch(crf_context* c, size_t need) {
+    crf::DeviceBuffer<unsigned char>& buf = c->grid.rank_scratch;
+    if (need <= buf.count()) return CRF_OK;
+    if (buf.reserve(need) != hipSuccess) {
+        (void)hipGetLastError();  // the failed allocation is reported here, not by the next launch
+        return fail(c, CRF_ERR_DEVICE, fmt("the sort needs %zu bytes of device memory, which could not be allocated", need));
+    }
+    return CRF_OK;
+}
+
 // The sort-based rank kernels' list of deferred voxels.  Set 0 serves the device entry points as well: the whole local
 // grid (num_voxels == alloc_voxels whenever no NarrowScope is active).  Set 1 only ever holds one range.
 int ensure_todo(crf_context* c) {
@@ -1636,6 +1648,74 @@ int crf_field_similarity(crf_context* c, int measure, int member, int num_bins, 
     }
     *out_value = value;
     if (out_samples) *out_samples = samples;
+    return CRF_OK;
+}
+
+// ---- ranks over all samples: the device-wide sort ---------------------------------------------------------------------------
+size_t crf_rank_scratch_bytes(const crf_context* c) { return c ? c->grid.rank_scratch.count() : 0; }
+
+int crf_rank_values_device(crf_context* c, const void* device_values, size_t count, void* device_ranks,
+                           unsigned long long* out_ranked) {
+    if (!c) return CRF_ERR_ARGUMENT;
+    if (out_ranked) *out_ranked = 0;
+    if (count == 0) return CRF_OK;
+    if (!device_values || !device_ranks) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (count > size_t(0x7FFFFFFF))
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%zu values: the sort carries 32-bit payloads (at most 2147483647)", count));
+    const char* in = static_cast<const char*>(device_values);
+    const char* out = static_cast<const char*>(device_ranks);
+    if (in < out + count * sizeof(float) && out < in + count * sizeof(float))
+        return fail(c, CRF_ERR_ARGUMENT, "crf_rank_values_device: the ranks overlap the values");
+    if (int r = bind_device(c)) return r;
+    if (int r = ensure_rank_scratch(c, crf::rank_sort_scratch_bytes(count))) return r;
+    TimedLaunch launch(c);
+    if (int r = launch.finish(crf::launch_rank_values(static_cast<const float*>(device_values), count,
+                                                      static_cast<float*>(device_ranks), c->grid.rank_scratch.get(),
+                                                      c->stream, launch.e0, launch.e1, out_ranked, &launch.info)))
+        return r;
+    CRF_HIP(c, hipStreamSynchronize(c->stream));
+    return CRF_OK;
+}
+
+// computeFieldSimilarity<double> with a rank measure (Similarity.cpp:134-143) on two resident fields.  An entry point of
+// its own: crf_field_similarity keeps refusing the rank measures.
+int crf_field_rank_similarity(crf_context* c, int measure, int member, float* out_value, unsigned long long* out_samples) {
+    if (int r = check_ready(c)) return r;
+    if (!out_value) return fail(c, CRF_ERR_ARGUMENT, "null output");
+    if (!c->grid.has_secondary())
+        return fail(c, CRF_ERR_STATE, "crf_field_rank_similarity needs secondary members (crf_upload_secondary_members)");
+    if (measure == CRF_KENDALL)
+        return fail(c, CRF_ERR_UNSUPPORTED, "crf_field_rank_similarity: Kendall needs an inversion count over all samples on top of "
+                                            "the sort, which is not implemented; Spearman is");
+    if (measure != CRF_SPEARMAN)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("crf_field_rank_similarity: measure %d is not a rank measure (crf_field_similarity "
+                                             "serves Pearson and binned MI)", measure));
+    if (member < -1 || member >= c->cs)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("member %d outside [-1, %d)", member, c->cs));
+    if (c->windowed)
+        return fail(c, CRF_ERR_UNSUPPORTED, "crf_field_rank_similarity does not evaluate windowed grids (member volumes of 4 GiB or more)");
+    const int members = member < 0 ? c->cs : 1;
+    if (size_t(members) * c->alloc_voxels > size_t(0x7FFFFFFF))
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%zu samples: the reference counts the samples of a field similarity in an int "
+                                                "(at most 2147483647)", size_t(members) * c->alloc_voxels));
+    if (int r = bind_device(c)) return r;
+    hipStream_t s = c->stream;
+    if (int r = ensure_wide(c, s)) return r;
+    if (int r = ensure_secondary_wide(c, s)) return r;
+    if (int r = ensure_workspace(c, crf::similarity_workspace_bytes())) return r;
+    if (int r = ensure_rank_scratch(c, crf::rank_similarity_scratch_bytes(members, c->alloc_voxels))) return r;
+    const crf_grid_state& g = c->grid;
+    const int first = member < 0 ? 0 : member;
+    crf::SimilarityJob job{c->view.members + first, c->view.secondary + first, members, c->alloc_voxels,
+                           g.members.vpt == 4 && g.secondary.vpt == 4, g.scratch[0].workspace.get()};
+    TimedLaunch launch(c);
+    if (int r = launch.finish(crf::launch_rank_similarity(job, g.rank_scratch.get(), s, launch.e0, launch.e1, &launch.info)))
+        return r;
+    double stats[7];
+    CRF_HIP(c, hipMemcpyAsync(stats, crf::similarity_stats(job.workspace), sizeof stats, hipMemcpyDeviceToHost, s));
+    CRF_HIP(c, hipStreamSynchronize(s));
+    *out_value = float(stats[6]);
+    if (out_samples) *out_samples = (unsigned long long)stats[0];
     return CRF_OK;
 }
 

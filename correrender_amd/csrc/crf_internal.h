@@ -394,6 +394,22 @@ hipError_t launch_similarity_histogram(const SimilarityJob& job, int num_bins, f
                                        float max_y, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
                                        LaunchInfo* info);
 
+// ---- kernels_rank_similarity.hip: ranks over a device array, and the rank form of the field similarity ----------------
+// Fractional ranks of `count` <= 2^31 - 1 fp32 values in input order (computeRanks, Correlation.cpp:277-303) by a
+// device-wide LSD radix sort; a NaN gets rank NaN and is not ranked.  d_ranks may be d_values itself (the values are read
+// once, before the first rank is stored) but must not overlap them otherwise.  scratch: rank_sort_scratch_bytes(count)
+// of device memory, 256-byte aligned.  SYNCHRONISES the stream once (the host reads the digit histograms back and leaves
+// out the passes that would move nothing); *ranked (may be null) is final on return, the ranks are stream-ordered.
+size_t rank_sort_scratch_bytes(size_t count);
+hipError_t launch_rank_values(const float* d_values, size_t count, float* d_ranks, unsigned char* scratch, hipStream_t s,
+                              hipEvent_t ev_begin, hipEvent_t ev_end, unsigned long long* ranked, LaunchInfo* info);
+// Spearman over the samples of a SimilarityJob: pairs with a NaN masked, ranks of x and of y, then
+// launch_similarity_moments over the two rank arrays (the results are where that launcher leaves them, in job.workspace).
+// scratch: rank_similarity_scratch_bytes(members, num_voxels).  One event pair around all launches.
+size_t rank_similarity_scratch_bytes(int members, size_t num_voxels);
+hipError_t launch_rank_similarity(const SimilarityJob& job, unsigned char* scratch, hipStream_t s, hipEvent_t ev_begin,
+                                  hipEvent_t ev_end, LaunchInfo* info);
+
 // ---- two vectors per item: the symmetric field mode and pair requests --------------------------------------------------
 // One evaluation of a measure between two member vectors per item.  Field mode (requests == nullptr): item v is voxel
 // pair (v, v), X = members_x[.][v] (the primary field), Y = members_y[.][v] (the secondary field).  Request mode: item r

@@ -471,6 +471,36 @@ class CorrField:
             C.c_float(minmax_x[1]), C.c_float(minmax_y[0]), C.c_float(minmax_y[1]), C.byref(value), C.byref(samples)))
         return (value.value, int(samples.value)) if return_samples else value.value
 
+    def rank_values(self, values, *, return_ranked: bool = False):
+        """Fractional ranks of a contiguous float32 CUDA tensor, in input order (the reference's computeRanks,
+        Correlation.cpp:277-303), by a device-wide radix sort: a new tensor of the same shape.  Equal values (-0 and +0
+        among them) share the mean of their positions; a NaN gets rank NaN and is not ranked.  With `return_ranked`:
+        (ranks, number of values ranked)."""
+        import torch
+        if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous():
+            raise ValueError("rank_values: a contiguous float32 CUDA tensor is required")
+        torch.cuda.current_stream(values.device).synchronize()   # the call runs on the context's own stream
+        ranks = torch.empty_like(values)
+        ranked = C.c_ulonglong()
+        self._check(self._lib.crf_rank_values_device(self._ctx, C.c_void_p(values.data_ptr()), values.numel(),
+                                                     C.c_void_p(ranks.data_ptr()), C.byref(ranked)))
+        return (ranks, int(ranked.value)) if return_ranked else ranks
+
+    def field_rank_similarity(self, measure, *, member: Optional[int] = None, return_samples: bool = False):
+        """computeFieldSimilarity<double> with a rank measure (Similarity.cpp:134-143) between the primary field (x) and
+        the secondary field (y): Spearman over the samples field_similarity() takes -- ranks of the kept x and of the kept
+        y over ALL samples (a device-wide sort), then the Pearson value of the two rank arrays.  Kendall is refused.
+        Returns the value, or (value, number of pairs kept) with `return_samples`."""
+        value, samples = C.c_float(), C.c_ulonglong()
+        self._check(self._lib.crf_field_rank_similarity(self._ctx, int(measure), -1 if member is None else int(member),
+                                                        C.byref(value), C.byref(samples)))
+        return (value.value, int(samples.value)) if return_samples else value.value
+
+    def rank_scratch_bytes(self) -> int:
+        """Device memory the sort of rank_values() / field_rank_similarity() currently holds (0 before first use;
+        set_grid releases it)."""
+        return int(self._lib.crf_rank_scratch_bytes(self._ctx))
+
     def tiled_element_count(self) -> int:
         return int(self._lib.crf_tiled_element_count(*self.grid))
 

@@ -130,7 +130,8 @@ int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_m
                                   crf_upload_members_format, crf_bind_members_device_format, crf_member_format,
                                   crf_last_member_format, crf_wide_copy_bytes, crf_window_count,
                                   crf_upload_secondary_members_format, crf_bind_secondary_members_device_format,
-                                  crf_secondary_member_format, crf_secondary_wide_copy_bytes, crf_field_similarity;
+                                  crf_secondary_member_format, crf_secondary_wide_copy_bytes, crf_field_similarity,
+                                  crf_rank_values_device, crf_field_rank_similarity, crf_rank_scratch_bytes;
                                4: crf_group_* (several devices behind one caller thread), crf_set_kraskov_noise;
                                3: crf_params.reserved[0] became prepared_slot (same layout; 0 keeps the old meaning) */
 
@@ -455,7 +456,8 @@ int crf_compute_dkl_device(crf_context* ctx, int estimator, int num_bins, int k,
  *                      forms the product in fp64: bit-identical to the object code up to 46 340 samples, well defined beyond.
  *   CRF_BINNED_MI_CC   sqrt(1 - exp(-2 MI)) of that float (Similarity.cpp:165-167).
  *   CRF_SPEARMAN, CRF_KENDALL, CRF_MI_KRASKOV, CRF_KMI_CC: CRF_ERR_UNSUPPORTED -- they need a global sort or a k-nearest-
- *                      neighbour search over all N samples.
+ *                      neighbour search over all N samples.  Spearman has an entry point of its own:
+ *                      crf_field_rank_similarity below.
  * Refusals (the context stays usable): no secondary members CRF_ERR_STATE; member outside [-1, cs) or num_bins outside
  * [1, 128] CRF_ERR_ARGUMENT; a windowed grid (crf_window_count > 1), or more than 2^31 - 1 candidate samples (the
  * reference counts samples in an int), CRF_ERR_UNSUPPORTED.  Members in a narrow format are read through their fp32
@@ -464,6 +466,47 @@ int crf_compute_dkl_device(crf_context* ctx, int estimator, int num_bins, int k,
 int crf_field_similarity(crf_context* ctx, int measure, int member, int num_bins,
                          float min_x, float max_x, float min_y, float max_y,
                          float* out_value, unsigned long long* out_samples /* may be NULL */);
+
+/* ---- ranks over all samples: a device-wide sort ----------------------------------------------------------------------------
+ * crf_rank_values_device: fractional ranks of `count` fp32 values on the device, in input order -- computeRanks
+ * (Correlation.cpp:277-303) -- by a device-wide radix sort (similarity_rank_sort_kernel and its siblings,
+ * kernels_rank_similarity.hip).  count at most 2^31 - 1; device_ranks holds count floats and must not overlap the input.
+ * Values compare as floats: -0 and +0 are equal, +-inf are ordinary values, the order among equal values does not matter.
+ * A run of m equal values whose first 1-based position in sorted order is s gets fl32(float(s) + float(m - 1) * 0.5f): one
+ * fp32 addition, no contraction.  That is the reference bit for bit up to 2^24 values (half ranks are rounded, not exact,
+ * from 2^23 on, there as here).
+ * ONE DELIBERATE DEVIATION: the reference carries s as an fp32 running sum (currentRank += float(numEqualValues)), which
+ * stops counting runs of one at 2^24; beyond 2^24 values its ranks are wrong (first seen at 2^24 + 4096 values).  This
+ * library forms s as an exact integer and rounds it once.
+ * A NaN gets rank NaN and is not ranked (the reference never ranks one: its gather removes them first); *out_ranked = the
+ * number of values ranked.  Synchronous on the context's own stream.
+ *
+ * crf_field_rank_similarity: the whole-field similarity by a rank measure (Similarity.cpp:134-143, the <double>
+ * instantiation), over the samples crf_field_similarity takes: every voxel of every member (member == -1) or of member
+ * `member`, pairs with a NaN on either side left out.
+ *   CRF_SPEARMAN   ranks of the kept x and of the kept y separately (as above), then the Pearson value of the two rank
+ *                  arrays by the moments path of crf_field_similarity: Sxy / (sqrt(Sxx) sqrt(Syy)) in fp64 with a fixed
+ *                  order, cast to float; bitwise reproducible from call to call.  No pair kept: 0; one pair, or a constant
+ *                  side: NaN.
+ *   CRF_KENDALL    CRF_ERR_UNSUPPORTED: it needs an inversion count over all samples on top of the sort.
+ *   every other measure: CRF_ERR_ARGUMENT (crf_field_similarity serves Pearson and binned MI).
+ * Refusals as for crf_field_similarity (the context stays usable): no secondary members CRF_ERR_STATE; member outside
+ * [-1, cs) CRF_ERR_ARGUMENT; a windowed grid, or more than 2^31 - 1 candidate samples, CRF_ERR_UNSUPPORTED.  Narrow
+ * members are read through their fp32 copies.  crf_last_kernel_name reports similarity_rank_sort_kernel; crf_set_profiling
+ * covers all launches of a call with one event pair.
+ *
+ * Scratch: the sort works in a buffer the context owns, grown on demand and released by crf_set_grid and crf_destroy
+ * (it is not part of the grid workspace: it can be tens of GiB).  crf_rank_values_device takes 16 bytes per value (a
+ * ping-pong of key and payload), crf_field_rank_similarity 24 bytes per candidate sample (the same, and the two rank
+ * arrays, which first hold the masked samples: nothing is compacted, a pair with a NaN is carried as (NaN, NaN)), both
+ * plus about 1 MiB of tables and count / 512 bytes.  A failed allocation gives CRF_ERR_DEVICE with the byte count in the
+ * message.  crf_rank_scratch_bytes: what the buffer currently holds, 0 before first use. */
+int crf_rank_values_device(crf_context* ctx, const void* device_values, size_t count,
+                           void* device_ranks /* count floats, must not overlap the input */,
+                           unsigned long long* out_ranked /* may be NULL */);
+int crf_field_rank_similarity(crf_context* ctx, int measure, int member,
+                              float* out_value, unsigned long long* out_samples /* may be NULL */);
+size_t crf_rank_scratch_bytes(const crf_context* ctx);
 
 /* ---- result layout for the renderer -------------------------------------------------------------------------------- */
 /* The reference keeps device fields in 8x8x4 tiles (bufferTileSize, VolumeData.cpp:1581-1621; addressed by IDXS of
