@@ -298,7 +298,7 @@ bool native_reduction(const crf_context* c) {
     return c->grid.format != CRF_MEMBER_F32 && c->grid.narrow.dword_aligned && !c->windowed;
 }
 
-// DKL reads narrow members element by element (kernels_dkl_narrow.hip: dkl_narrow_kernel; the element's own alignment), at
+// DKL reads narrow members element by element (kernels_dkl.hip: dkl_kernel at a narrow FMT, reported as dkl_narrow_kernel; the element's own alignment), at
 // any member count, where that was measured to be no slower than dkl_kernel on the copy (crf_internal.h: dkl_narrow_routed;
 // profiles/narrow_dkl_ab.md).  CRF_DKL_COUNTING_SORT and CRF_DKL_BLOCKS_PER_CU move a native call as they move an fp32 call.
 bool native_dkl(const crf_context* c, int estimator, int k) {

@@ -401,6 +401,17 @@ __device__ __forceinline__ float narrow_code_value(uint32_t code) {
     }
 }
 
+// One element of a member of ANY stored format, streamed once, as the value the calculators see: the front end of the
+// kernels that are one template for all four formats (dkl_kernel, mi_kraskov_kernel) and the only place in them that knows
+// how a member is stored, besides the element size (member_format_bytes(FMT)) behind their byte offsets.
+template <int FMT>
+__device__ __forceinline__ float member_value_nt(const void* base, uint32_t bytes, uint32_t byte_offset) {
+    if constexpr (FMT == CRF_MEMBER_F32)
+        return load_member_nt(static_cast<const float*>(base), bytes, byte_offset);
+    else
+        return narrow_code_value<FMT>(load_code_nt<FMT>(base, bytes, byte_offset));
+}
+
 // The voxel side of computePearson2<float> (Correlation.cpp:141-174) for one lane: y[0..cs) in registers, a_e =
 // invNm1 * ((x_e - meanX) / sdX) prepared once per evaluation.  Sequential fp32, no contraction.
 // SURE: slots 0..SURE-1 are members whatever cs is (the caller's contract), so only the slots behind them are guarded.

@@ -1,8 +1,5 @@
-// crf_dkl_device.h -- what the two DKL kernel families share: dkl_kernel<NS> (kernels_dkl.hip, fp32 members) and
-// dkl_narrow_kernel<FMT, NS> (kernels_dkl_narrow.hip, members stored as uint8, uint16 or float16).  Tile and table sizes,
-// the window descent of the k-NN estimator, and the launch (launch_dkl_family: instantiation choice, LDS or workspace,
-// grid sizing, the tuning switches).  The kernel bodies are not here: each file holds its own (kernels_dkl_narrow.hip says
-// why).
+// crf_dkl_device.h -- the parts of dkl_kernel<FMT, NS> (kernels_dkl.hip) that stand on their own: tile and table sizes
+// (host and device) and the window descent of the k-NN estimator.  Nothing here depends on how the members are stored.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -118,71 +115,6 @@ __device__ float dkl_window_distance(const float* data, int N, int k, int i) {
         lo += (here < left && here < right) ? 0 : towards * step;
     }
     return w.cost(lo);
-}
-
-// The launch of one kernel family.  KERNELS names it: Member (float, or void for a narrow format), name (what LaunchInfo
-// reports) and instance<NS>() (the kernel of network size NS).  Instantiation choice, LDS / workspace decision, grid
-// sizing and the two tuning switches are the same for every family: the tile holds converted floats whatever was loaded.
-template <class KERNELS>
-hipError_t launch_dkl_family(const typename KERNELS::Member* const* d_members, int cs, size_t num_voxels, int estimator,
-                             int num_bins, int k, double knn_const, unsigned char* d_workspace, float* d_out,
-                             hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
-    const size_t tiles = (num_voxels + 63) / 64;
-    unsigned blocks = unsigned(tiles < size_t(kDklBlocks) ? tiles : size_t(kDklBlocks));
-    const char* counting = getenv("CRF_DKL_COUNTING_SORT");  // tuning / tests: the O(cs^2) column sort for every cs
-    const bool plain = counting && *counting == '1';
-    // network instantiations: the k-NN estimator up to 128 members, the binned estimator up to 96 (registers only)
-    const bool binned_registers = estimator == 0 && cs <= 96 && !plain;
-    const bool network_sort = (estimator == 1 && cs <= 128 && !plain) || binned_registers;
-    // k-NN with k <= 2 up to 96 members runs entirely in registers (see the kernel): no LDS column, so the occupancy is
-    // the registers' alone
-    const bool register_descent = estimator == 1 && network_sort && k <= 2 && cs >= 4 && cs <= 96;
-    const size_t tile = (register_descent || binned_registers) ? 0 : dkl_tile_bytes(cs, estimator, num_bins, network_sort);
-    const bool use_lds = tile <= kDklLdsLimit;  // (one column of <= 128 members always fits)
-    if (!use_lds && !d_workspace) return hipErrorInvalidValue;
-    const size_t lds_bytes = dkl_log_table_bytes(cs, estimator) + (use_lds ? tile : 0);
-    if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    // persistent grid = the blocks the chip holds at once, asked from the runtime per instantiation (registers and the
-    // LDS tile decide; a grid one block per CU larger than that runs a second round: measured 13.9 -> 18.5 ms)
-#define CRF_LAUNCH_DKL(NS)                                                                                              \
-    if (use_lds) {                                                                                                      \
-        int per_cu = 0, cus = 256;                                                                                      \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNELS::template instance<NS>(), 64, lds_bytes) ==   \
-                hipSuccess &&                                                                                           \
-            per_cu > 0) {                                                                                               \
-            /* the runtime's answer was one block high for both estimators (LDS is handed out in 1280-byte granules:  \
-               160 KB / 128); a grid one block per CU too large runs a second round: 11.1 -> 18.6 ms (binned), 17.5 -> \
-               31.0 ms (k-NN, two columns) */                                                                          \
-            const size_t granules = (lds_bytes + 1279) / 1280;                                                          \
-            const int by_lds = granules ? int(128 / granules) : per_cu;                                                 \
-            per_cu = std::max(1, std::min(per_cu, by_lds));                                                             \
-            int dev = 0;                                                                                                \
-            (void)hipGetDevice(&dev);                                                                                   \
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);                              \
-            if (const char* ov = getenv("CRF_DKL_BLOCKS_PER_CU"); ov && atoi(ov) > 0) per_cu = atoi(ov); /* tuning */    \
-            const size_t resident = size_t(cus > 0 ? cus : 256) * size_t(per_cu);                                       \
-            blocks = unsigned(tiles < resident ? tiles : resident);                                                     \
-        }                                                                                                               \
-    }                                                                                                                   \
-    hipLaunchKernelGGL(KERNELS::template instance<NS>(), dim3(blocks), dim3(64), lds_bytes, s, d_members, d_out,        \
-                       num_voxels, cs, estimator, num_bins, k, knn_const, 0.5 * double(std::log(kSglTwoPi)),            \
-                       use_lds ? nullptr : d_workspace)
-    const int network = network_sort ? (cs + 15) / 16 : 0;
-    switch (network) {
-        case 1: CRF_LAUNCH_DKL(16); break;
-        case 2: CRF_LAUNCH_DKL(32); break;
-        case 3: CRF_LAUNCH_DKL(48); break;
-        case 4: CRF_LAUNCH_DKL(64); break;
-        case 5: CRF_LAUNCH_DKL(80); break;
-        case 6: CRF_LAUNCH_DKL(96); break;
-        case 7: CRF_LAUNCH_DKL(112); break;
-        case 8: CRF_LAUNCH_DKL(128); break;
-        default: CRF_LAUNCH_DKL(0); break;
-    }
-#undef CRF_LAUNCH_DKL
-    if (ev_end) (void)hipEventRecord(ev_end, s);
-    if (info) info->kernel_name = KERNELS::name;
-    return hipGetLastError();
 }
 
 }  // namespace

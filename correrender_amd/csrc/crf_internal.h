@@ -167,7 +167,7 @@ constexpr int kNarrowMaxMembers = 128;
 // A narrow member must be smaller than this: the native kernel's 32-bit voxel index and byte offset of the last block's
 // surplus lanes (up to 1020 voxels past the end) must not wrap.
 constexpr size_t kNarrowMaxBytes = size_t(0xFFFF0000u);
-inline size_t member_format_bytes(int format) {
+constexpr size_t member_format_bytes(int format) {
     return format == CRF_MEMBER_U8 ? 1 : format == CRF_MEMBER_F32 ? 4 : 2;
 }
 // d_narrow: cs device pointers to num_voxels elements of `format` each, every one 4-byte aligned; num_voxels x element
@@ -339,7 +339,7 @@ size_t dkl_workspace_bytes(int cs, int estimator, int num_bins, size_t num_voxel
 hipError_t launch_dkl(const float* const* d_members, int cs, size_t num_voxels, int estimator, int num_bins, int k,
                       double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s, hipEvent_t ev_begin,
                       hipEvent_t ev_end, LaunchInfo* info);
-// ---- kernels_dkl_narrow.hip: DKL on narrow members, read as stored ---------------------------------------------------
+// ---- kernels_dkl.hip: DKL on narrow members, read as stored (dkl_kernel<FMT, NS> at a narrow FMT) --------------------
 // Any cs in 1..kMaxGenericMembers, both estimators, bit-identical to launch_dkl on the converted values; the workspace is
 // launch_dkl's (dkl_workspace_bytes: the columns hold converted floats).  d_narrow: cs device pointers to num_voxels
 // elements of `format`, each aligned to its element (no more); num_voxels x element size below kNarrowMaxBytes.  One event

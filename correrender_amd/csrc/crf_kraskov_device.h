@@ -16,6 +16,17 @@ static_assert(size_t(((2 * kDxtMaxMembers + 7) / 8 * 8) + 128 * 128) * sizeof(do
 
 constexpr double kCountSlack = 1e-15;  // default_epsilon<double>::value, MutualInformation.cpp:163
 
+// mi_kraskov_kernel<FMT, K, TI, DXT> (kernels_kraskov.hip), one wave per tile of 64 voxels, whatever FMT is:
+// (members, prep, psi, noise_query, out, num_voxels, cs, k, estimator, to_cc, c_term).  Its dynamic LDS: four tables of
+// doubles (px, sorted px, noise_query, psi(0..cs) padded to 16 bytes) and the cs x 64 column of converted floats.
+using KraskovColumnKernel = void (*)(const void* const*, const double*, const double*, const double*, float*, size_t, int,
+                                     int, int, int, double);
+constexpr size_t kraskov_column_lds_bytes(int cs) {
+    return size_t(4 * cs + 1 + ((cs + 1) & 1)) * sizeof(double) + size_t(cs) * 64 * sizeof(float);
+}
+// the instantiation for a Column plan on narrow members (kernels_kraskov.hip); nullptr where none is built
+KraskovColumnKernel kraskov_column_narrow_kernel(int format, const KraskovPlan& p);
+
 // fp64 min / max / Chebyshev distance as single instructions.  fmin()/fmax() make hipcc canonicalise each operand first
 // (an extra v_max_f64 x, x); the operands here are never signalling NaNs and the k-select only needs "one of the two".
 __device__ __forceinline__ double min_f64(double a, double b) {

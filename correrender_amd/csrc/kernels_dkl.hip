@@ -10,6 +10,10 @@
 // compares) and then plays the reference's step-halving window descent (KnnWindow below) in fp32.  4*cs + 4 algorithmic bytes
 // per voxel; VALU/LDS bound.  fp64 log/exp come from the device math library (<= 1 ulp from the host's): results agree
 // with the CPU restatement to ~1e-15 before the cast to float (tolerance 1e-5 relative, tests/test_gpu_dkl.py).
+//
+// One kernel text for members stored as fp32, uint8, uint16 or float16, read as stored (template argument FMT): the
+// arithmetic and its order exist once, and the fp32 instantiations are instruction for instruction what they were as a
+// kernel of their own (profiles/member_format_templates.md).  tests/test_gpu_narrow_dkl.py compares the formats bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -31,11 +35,19 @@ size_t dkl_workspace_bytes(int cs, int estimator, int num_bins, size_t num_voxel
 // NS: size of the sorting network of the k-NN estimator's column sort (a multiple of 16 >= cs, at most 128), or 0: sort by
 // counting (any member count; also the instantiation the binned estimator runs).  One kernel per network size -- all
 // eight networks inside one kernel cost 512 registers and scratch.
-template <int NS>
-__global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(const float* const* __restrict__ members, float* __restrict__ out,
+// FMT: how the members are stored (CRF_MEMBER_*).  A lane loads one float, byte or short per member and member_value_nt
+// (crf_device.h) makes it the fp32 value the calculators see; from there on nothing depends on FMT: the LDS / workspace
+// column holds converted floats, so a narrow format's results are bit-identical to the fp32 instantiation's on the
+// converted values, and tile sizes, workspace and grid sizing are the same for all four.  num_voxels x element size is
+// below kNarrowMaxBytes (checked at upload / bind), so no byte offset wraps and kOutOfRangeOffset stays past the end of
+// every member: a padded slot reads 0.
+template <int FMT, int NS>
+__global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(const void* const* __restrict__ members, float* __restrict__ out,
                                                  size_t num_voxels, int cs, int estimator, int num_bins, int k,
                                                  double knn_const, double half_log_two_pi,
                                                  unsigned char* __restrict__ workspace) {
+    static_assert(FMT == CRF_MEMBER_F32 || FMT == CRF_MEMBER_U8 || FMT == CRF_MEMBER_U16 || FMT == CRF_MEMBER_F16, "a member format");
+    constexpr uint32_t kElement = uint32_t(member_format_bytes(FMT));
     extern __shared__ __align__(16) unsigned char smem[];
     // LDS: [ln(h), h = 0..cs, of the binned estimator (dkl_log_table_bytes)] [the tile, unless it lives in the workspace]
     double* s_logn = reinterpret_cast<double*>(smem);
@@ -53,7 +65,7 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
     float* vals = reinterpret_cast<float*>(tile) + lane;
     float* sorted = kInPlace ? vals : vals + size_t(cs) * 64;                                  // k-NN
     uint16_t* hist = reinterpret_cast<uint16_t*>(tile + size_t(cs) * 64 * sizeof(float)) + lane;  // binned
-    const uint32_t bytes = uint32_t(num_voxels) * 4u;
+    const uint32_t bytes = uint32_t(num_voxels) * kElement;
     const size_t tiles = (num_voxels + 63) / 64;
     const float qnan = __uint_as_float(0x7FC00000u);
     const double factor = 1.0 / double(cs);
@@ -61,7 +73,7 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
     for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const size_t v = t * 64 + lane;
         const bool active = v < num_voxels;
-        const uint32_t byte_offset = active ? uint32_t(v) * 4u : kOutOfRangeOffset;
+        const uint32_t byte_offset = active ? uint32_t(v) * kElement : kOutOfRangeOffset;
         bool is_nan = false;
         double mean = 0.0;
         double variance = 0.0;
@@ -72,8 +84,13 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
             int cs_p = cs;  // (laundered per phase: keeps the compiler from carrying NS uniform member-count tests as
             asm volatile("" : "+s"(cs_p));  // SGPR pairs across the persistent tile loop)
 #pragma unroll
-            for (int e = 0; e < NS; e++)
-                x[e] = load_member_nt(members[e < cs_p ? e : cs_p - 1], bytes, e < cs_p ? byte_offset : kOutOfRangeOffset);
+            for (int e = 0; e < NS; e++) {
+                x[e] = member_value_nt<FMT>(members[e < cs_p ? e : cs_p - 1], bytes, e < cs_p ? byte_offset : kOutOfRangeOffset);
+                // float(h) is one v_cvt, and with the conversion visible to the later phases the float16 instantiations
+                // came out with 180 / 244 VGPRs at NS = 32 / 48 against the fp32 ones' 149 / 197, and 180 B of scratch at NS =
+                // 64.  Behind the empty asm the phases see an opaque fp32 value, as the fp32 ones do: the same registers.
+                if constexpr (FMT == CRF_MEMBER_F16) asm("" : "+v"(x[e]));
+            }
             asm volatile("" : "+s"(cs_p));
 #pragma unroll
             for (int e = 0; e < NS; e++) {
@@ -93,7 +110,7 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
         } else {
 #pragma unroll 4
             for (int e = 0; e < cs; e++) {
-                const float xe = load_member_nt(members[e], bytes, byte_offset);
+                const float xe = member_value_nt<FMT>(members[e], bytes, byte_offset);
                 is_nan |= xe != xe;
                 vals[e * 64] = xe;
                 mean += factor * double(xe);
@@ -359,21 +376,96 @@ __global__ __launch_bounds__(64, (NS > 0 && NS <= 64) ? 2 : 1) void dkl_kernel(c
 }
 
 namespace {
-struct DklKernels {
-    using Member = float;
-    static constexpr const char* name = "dkl_kernel";
-    template <int NS>
-    static constexpr auto instance() {
-        return &dkl_kernel<NS>;
+
+// The launch for members of format FMT.  Instantiation choice, LDS / workspace decision, grid sizing and the two tuning
+// switches do not depend on the format: the tile holds converted floats whatever was loaded.  LaunchInfo keeps the two
+// names the kernels had as separate texts: "dkl_kernel" for fp32 members, "dkl_narrow_kernel" for the narrow formats.
+template <int FMT>
+hipError_t launch_dkl_format(const void* const* d_members, int cs, size_t num_voxels, int estimator, int num_bins, int k,
+                             double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s,
+                             hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    const size_t tiles = (num_voxels + 63) / 64;
+    unsigned blocks = unsigned(tiles < size_t(kDklBlocks) ? tiles : size_t(kDklBlocks));
+    const char* counting = getenv("CRF_DKL_COUNTING_SORT");  // tuning / tests: the O(cs^2) column sort for every cs
+    const bool plain = counting && *counting == '1';
+    // network instantiations: the k-NN estimator up to 128 members, the binned estimator up to 96 (registers only)
+    const bool binned_registers = estimator == 0 && cs <= 96 && !plain;
+    const bool network_sort = (estimator == 1 && cs <= 128 && !plain) || binned_registers;
+    // k-NN with k <= 2 up to 96 members runs entirely in registers (see the kernel): no LDS column, so the occupancy is
+    // the registers' alone
+    const bool register_descent = estimator == 1 && network_sort && k <= 2 && cs >= 4 && cs <= 96;
+    const size_t tile = (register_descent || binned_registers) ? 0 : dkl_tile_bytes(cs, estimator, num_bins, network_sort);
+    const bool use_lds = tile <= kDklLdsLimit;  // (one column of <= 128 members always fits)
+    if (!use_lds && !d_workspace) return hipErrorInvalidValue;
+    const size_t lds_bytes = dkl_log_table_bytes(cs, estimator) + (use_lds ? tile : 0);
+    if (ev_begin) (void)hipEventRecord(ev_begin, s);
+    // persistent grid = the blocks the chip holds at once, asked from the runtime per instantiation (registers and the
+    // LDS tile decide; a grid one block per CU larger than that runs a second round: measured 13.9 -> 18.5 ms)
+#define CRF_LAUNCH_DKL(NS)                                                                                              \
+    if (use_lds) {                                                                                                      \
+        int per_cu = 0, cus = 256;                                                                                      \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dkl_kernel<FMT, NS>, 64, lds_bytes) == hipSuccess &&  \
+            per_cu > 0) {                                                                                               \
+            /* the runtime's answer was one block high for both estimators (LDS is handed out in 1280-byte granules:  \
+               160 KB / 128); a grid one block per CU too large runs a second round: 11.1 -> 18.6 ms (binned), 17.5 -> \
+               31.0 ms (k-NN, two columns) */                                                                          \
+            const size_t granules = (lds_bytes + 1279) / 1280;                                                          \
+            const int by_lds = granules ? int(128 / granules) : per_cu;                                                 \
+            per_cu = std::max(1, std::min(per_cu, by_lds));                                                             \
+            int dev = 0;                                                                                                \
+            (void)hipGetDevice(&dev);                                                                                   \
+            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);                              \
+            if (const char* ov = getenv("CRF_DKL_BLOCKS_PER_CU"); ov && atoi(ov) > 0) per_cu = atoi(ov); /* tuning */    \
+            const size_t resident = size_t(cus > 0 ? cus : 256) * size_t(per_cu);                                       \
+            blocks = unsigned(tiles < resident ? tiles : resident);                                                     \
+        }                                                                                                               \
+    }                                                                                                                   \
+    hipLaunchKernelGGL((dkl_kernel<FMT, NS>), dim3(blocks), dim3(64), lds_bytes, s, d_members, d_out, num_voxels, cs,   \
+                       estimator, num_bins, k, knn_const, 0.5 * double(std::log(kSglTwoPi)),                            \
+                       use_lds ? nullptr : d_workspace)
+    const int network = network_sort ? (cs + 15) / 16 : 0;
+    switch (network) {
+        case 1: CRF_LAUNCH_DKL(16); break;
+        case 2: CRF_LAUNCH_DKL(32); break;
+        case 3: CRF_LAUNCH_DKL(48); break;
+        case 4: CRF_LAUNCH_DKL(64); break;
+        case 5: CRF_LAUNCH_DKL(80); break;
+        case 6: CRF_LAUNCH_DKL(96); break;
+        case 7: CRF_LAUNCH_DKL(112); break;
+        case 8: CRF_LAUNCH_DKL(128); break;
+        default: CRF_LAUNCH_DKL(0); break;
     }
-};
+#undef CRF_LAUNCH_DKL
+    if (ev_end) (void)hipEventRecord(ev_end, s);
+    if (info) info->kernel_name = FMT == CRF_MEMBER_F32 ? "dkl_kernel" : "dkl_narrow_kernel";
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_dkl(const float* const* d_members, int cs, size_t num_voxels, int estimator, int num_bins, int k,
                       double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s, hipEvent_t ev_begin,
                       hipEvent_t ev_end, LaunchInfo* info) {
-    return launch_dkl_family<DklKernels>(d_members, cs, num_voxels, estimator, num_bins, k, knn_const, d_workspace, d_out,
-                                         s, ev_begin, ev_end, info);
+    return launch_dkl_format<CRF_MEMBER_F32>(reinterpret_cast<const void* const*>(d_members), cs, num_voxels, estimator,
+                                             num_bins, k, knn_const, d_workspace, d_out, s, ev_begin, ev_end, info);
+}
+
+hipError_t launch_dkl_narrow(const void* const* d_narrow, int format, int cs, size_t num_voxels, int estimator, int num_bins,
+                             int k, double knn_const, unsigned char* d_workspace, float* d_out, hipStream_t s,
+                             hipEvent_t ev_begin, hipEvent_t ev_end, LaunchInfo* info) {
+    if (format != CRF_MEMBER_U8 && format != CRF_MEMBER_U16 && format != CRF_MEMBER_F16) return hipErrorInvalidValue;
+    if (num_voxels * member_format_bytes(format) >= kNarrowMaxBytes) return hipErrorInvalidValue;
+    switch (format) {
+        case CRF_MEMBER_U8:
+            return launch_dkl_format<CRF_MEMBER_U8>(d_narrow, cs, num_voxels, estimator, num_bins, k, knn_const, d_workspace,
+                                                    d_out, s, ev_begin, ev_end, info);
+        case CRF_MEMBER_U16:
+            return launch_dkl_format<CRF_MEMBER_U16>(d_narrow, cs, num_voxels, estimator, num_bins, k, knn_const, d_workspace,
+                                                     d_out, s, ev_begin, ev_end, info);
+        default:
+            return launch_dkl_format<CRF_MEMBER_F16>(d_narrow, cs, num_voxels, estimator, num_bins, k, knn_const, d_workspace,
+                                                     d_out, s, ev_begin, ev_end, info);
+    }
 }
 
 }  // namespace crf

@@ -68,14 +68,19 @@ __global__ __launch_bounds__(256) void kraskov_prep_kernel(RefSource src, const 
 
 // The K = k <= 4 nearest OTHER points are kept in registers (sorted insertion: min/max only; a kd-tree returns at most
 // cs points, so the host passes K = min(k, cs - 1)).  TI points are processed concurrently per lane.
-template <int K, int TI, bool DXT = false>
-__global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __restrict__ members,
+// FMT: how the members are stored (CRF_MEMBER_*).  member_value_nt (crf_device.h) makes the one float, byte or short a
+// lane loads per member the fp32 value the calculators see and the lane's LDS column holds those floats; nothing after the
+// load depends on FMT, so a narrow format's results are bit-identical to the fp32 instantiation's of the same (K, TI, DXT)
+// on the converted values.  (num_voxels x element size is below kNarrowMaxBytes: no byte offset wraps.)
+template <int FMT, int K, int TI, bool DXT = false>
+__global__ __launch_bounds__(64) void mi_kraskov_kernel(const void* const* __restrict__ members,
                                                         const double* __restrict__ prep_px,
                                                         const double* __restrict__ table_psi,
                                                         const double* __restrict__ noise_query,
                                                         float* __restrict__ out, size_t num_voxels, int cs, int k,
                                                         int estimator, int to_cc, double c_term) {
-    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr uint32_t kElement = uint32_t(member_format_bytes(FMT));
+    extern __shared__ __align__(16) unsigned char smem[];  // kraskov_column_lds_bytes(cs)
     double* s_px = reinterpret_cast<double*>(smem);  // member order
     double* s_spx = s_px + cs;                       // ascending
     double* s_nq = s_spx + cs;
@@ -89,12 +94,12 @@ __global__ __launch_bounds__(64) void mi_kraskov_kernel(const float* const* __re
     }
     for (int i = lane; i <= cs; i += 64) s_psi[i] = table_psi[i];
     const size_t v = size_t(blockIdx.x) * 64 + lane;
-    const uint32_t byte_offset = uint32_t(v) * 4u, bytes = uint32_t(num_voxels) * 4u;  // lanes past the end read 0
+    const uint32_t byte_offset = uint32_t(v) * kElement, bytes = uint32_t(num_voxels) * kElement;  // lanes past the end read 0
     bool is_nan = false;
 #pragma unroll 8
     for (int e = 0; e < cs; e++) {
-        const float y = load_member_nt(members[e], bytes, byte_offset);
-        is_nan |= (y != y);
+        const float y = member_value_nt<FMT>(members[e], bytes, byte_offset);
+        if constexpr (FMT == CRF_MEMBER_F32 || FMT == CRF_MEMBER_F16) is_nan |= (y != y);  // the integer formats have no NaN
         s_y[e * 64 + lane] = y;
     }
     __syncthreads();
@@ -791,23 +796,39 @@ void launch_kraskov_prep(const RefSource& ref, const float* const* d_members, in
 
 namespace {
 
-// mi_kraskov_kernel and kraskov_sorted_kernel: (members, prep, psi, noise_query, out, num_voxels, cs, k, estimator, to_cc,
-// c_term); kraskov_direct_kernel: members_x after members, share after c_term
+// kraskov_sorted_kernel: (members, prep, psi, noise_query, out, num_voxels, cs, k, estimator, to_cc, c_term), which are
+// mi_kraskov_kernel's arguments too (KraskovColumnKernel, crf_kraskov_device.h: its members are const void*);
+// kraskov_direct_kernel: members_x after members, share after c_term
 using TileKernel = void (*)(const float* const*, const double*, const double*, const double*, float*, size_t, int, int,
                             int, int, double);
 using DirectKernel = void (*)(const float* const*, const float* const*, const double*, const double*, const double*,
                               float*, size_t, int, int, int, int, double, int);
 
-TileKernel column_kernel(const KraskovPlan& p) {
-    switch (p.K) {
-        case 1: return p.dxt ? mi_kraskov_kernel<1, 8, true> : mi_kraskov_kernel<1, 8>;
-        case 2:
-            if (p.TI == 16) return mi_kraskov_kernel<2, 16>;
-            return p.dxt ? mi_kraskov_kernel<2, 8, true> : mi_kraskov_kernel<2, 8>;
-        case 3:
-            if (p.TI == 16) return mi_kraskov_kernel<3, 16>;
-            return p.dxt ? mi_kraskov_kernel<3, 8, true> : mi_kraskov_kernel<3, 8>;
-        default: return p.dxt ? mi_kraskov_kernel<4, 4, true> : mi_kraskov_kernel<4, 4>;
+// Only what the plans route is built.  fp32: every (K, TI, table) kraskov_field_plan can ask for.  Narrow members: uint8
+// with K = 2, 3 and 8 points per sweep, which is what kraskov_narrow_plan sends to the column kernel (33..48 members; the
+// plan takes 16 points per sweep only above 56).  nullptr for everything else.
+template <int FMT>
+KraskovColumnKernel column_kernel(const KraskovPlan& p) {
+    if constexpr (FMT == CRF_MEMBER_F32) {
+        switch (p.K) {
+            case 1: return p.dxt ? mi_kraskov_kernel<FMT, 1, 8, true> : mi_kraskov_kernel<FMT, 1, 8>;
+            case 2:
+                if (p.TI == 16) return mi_kraskov_kernel<FMT, 2, 16>;
+                return p.dxt ? mi_kraskov_kernel<FMT, 2, 8, true> : mi_kraskov_kernel<FMT, 2, 8>;
+            case 3:
+                if (p.TI == 16) return mi_kraskov_kernel<FMT, 3, 16>;
+                return p.dxt ? mi_kraskov_kernel<FMT, 3, 8, true> : mi_kraskov_kernel<FMT, 3, 8>;
+            default: return p.dxt ? mi_kraskov_kernel<FMT, 4, 4, true> : mi_kraskov_kernel<FMT, 4, 4>;
+        }
+    } else if constexpr (FMT == CRF_MEMBER_U8) {
+        if (p.TI != 8) return nullptr;
+        switch (p.K) {
+            case 2: return p.dxt ? mi_kraskov_kernel<FMT, 2, 8, true> : mi_kraskov_kernel<FMT, 2, 8>;
+            case 3: return p.dxt ? mi_kraskov_kernel<FMT, 3, 8, true> : mi_kraskov_kernel<FMT, 3, 8>;
+            default: return nullptr;
+        }
+    } else {
+        return nullptr;
     }
 }
 
@@ -892,12 +913,11 @@ hipError_t launch_field(const KraskovPlan& p, const float* const* d_members, int
                                kraskov_table_bytes(cs), s, d_members, prep, t.psi, t.noise_query, d_out, num_voxels, cs, a.k,
                                a.estimator, int(a.to_cc), a.c_term);
             break;
-        case KraskovFamily::Column: {  // one wave per tile: four tables (psi padded to 16 bytes) and the cs x 64 column
-            const size_t lds = size_t(4 * cs + 1 + ((cs + 1) & 1)) * sizeof(double) + size_t(cs) * 64 * sizeof(float);
-            hipLaunchKernelGGL(column_kernel(p), dim3(unsigned(tiles)), dim3(64), lds, s, d_members, prep, t.psi,
-                               t.noise_query, d_out, num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term);
+        case KraskovFamily::Column:  // one wave per tile
+            hipLaunchKernelGGL(column_kernel<CRF_MEMBER_F32>(p), dim3(unsigned(tiles)), dim3(64), kraskov_column_lds_bytes(cs),
+                               s, reinterpret_cast<const void* const*>(d_members), prep, t.psi, t.noise_query, d_out,
+                               num_voxels, cs, a.k, a.estimator, int(a.to_cc), a.c_term);
             break;
-        }
     }
     if (ev_end) (void)hipEventRecord(ev_end, s);
     if (info)
@@ -908,6 +928,10 @@ hipError_t launch_field(const KraskovPlan& p, const float* const* d_members, int
 }
 
 }  // namespace
+
+KraskovColumnKernel kraskov_column_narrow_kernel(int format, const KraskovPlan& p) {
+    return format == CRF_MEMBER_U8 ? column_kernel<CRF_MEMBER_U8>(p) : nullptr;
+}
 
 // 2..128 members: whichever kernel kraskov_field_plan picks
 hipError_t launch_mi_kraskov(const float* const* d_members, int cs, size_t num_voxels, const RefSource& ref,

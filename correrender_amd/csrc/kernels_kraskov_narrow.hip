@@ -1,5 +1,6 @@
 // kernels_kraskov_narrow.hip -- Kraskov (KSG) mutual information on members stored as uint8, uint16 or float16, read as
-// stored: the siblings of mi_kraskov_kernel and kraskov_direct_kernel (kernels_kraskov.hip), whose text stays as it is.
+// stored: the launch of both kernel families, and kraskov_direct_narrow_kernel, the sibling of kraskov_direct_kernel
+// (kernels_kraskov.hip).
 //
 // A lane owns one voxel and loads one byte / short per member (load_code_nt, the element's own alignment); the code
 // becomes the value the calculators see through narrow_code_value (crf_device.h: the correctly rounded float(b) / 255.0f,
@@ -7,12 +8,12 @@
 // (kraskov_field_plan) fixes family, K, TI and the x-distance table, and with them the order in which the fp64 partial
 // sums are added, so the results are bit-identical to the fp32 kernel of the same plan on the converted values.
 //
-// Both kernels are copies of the fp32 kernels' text -- mi_kraskov_kernel, and the share = 1 / STAGE path of
-// kraskov_direct_kernel without its symmetric form -- with another front end: the fp32 kernels'
-// registers, scratch and LDS must stay what they are, and a body shared with a narrow kernel moved those of the binned
-// kernel (profiles/narrow_binned_ab.md).  Whoever changes the arithmetic or the order of
-// the sums in kernels_kraskov.hip has to make the same change here: tests/test_gpu_narrow_kraskov.py compares the two bit
-// for bit at every routed plan.
+// The column kernel is not here: mi_kraskov_kernel<FMT, K, TI, DXT> (kernels_kraskov.hip) is one text for every stored
+// format, and this file launches its uint8 instantiations (kraskov_column_narrow_kernel).  The tile-free kernel below is a
+// text of its own, and not a copy of kraskov_direct_kernel's: it always stages the tile, it has PARK, and it leaves out
+// the symmetric form and the share == 0 path that the fp32 kernel keeps.  Its arithmetic and the order of its sums are
+// those of kraskov_direct_kernel's share = 1 path, which a change there has to keep in mind:
+// tests/test_gpu_narrow_kraskov.py compares the two bit for bit at every routed plan.
 //
 // Where a value lives between its one load and its uses is not arithmetic.  The column kernel parks converted floats; the
 // tile-free kernel has PARK:
@@ -49,184 +50,6 @@ template <int FMT, int PARK>
 __device__ __forceinline__ float kraskov_parked_value(kraskov_parked_t<FMT, PARK> parked) {
     if constexpr (PARK == kParkFloats) return parked;
     else return narrow_code_value<FMT>(uint32_t(parked));
-}
-
-// mi_kraskov_kernel on narrow members: the lane's LDS column holds the converted floats, as the fp32 kernel's does.
-template <int FMT, int K, int TI, bool DXT = false>
-__global__ __launch_bounds__(64) void mi_kraskov_narrow_kernel(const void* const* __restrict__ members,
-                                                               const double* __restrict__ prep_px,
-                                                               const double* __restrict__ table_psi,
-                                                               const double* __restrict__ noise_query,
-                                                               float* __restrict__ out, size_t num_voxels, int cs, int k,
-                                                               int estimator, int to_cc, double c_term) {
-    constexpr uint32_t kElement = FMT == CRF_MEMBER_U8 ? 1u : 2u;
-    extern __shared__ __align__(16) unsigned char smem[];
-    double* s_px = reinterpret_cast<double*>(smem);  // member order
-    double* s_spx = s_px + cs;                       // ascending
-    double* s_nq = s_spx + cs;
-    double* s_psi = s_nq + cs;                                                  // cs + 1 entries: psi(0..cs)
-    float* s_y = reinterpret_cast<float*>(s_psi + (cs + 1) + ((cs + 1) & 1));  // keep 16-byte alignment
-    const int lane = threadIdx.x;
-    for (int i = lane; i < cs; i += 64) {
-        s_px[i] = prep_px[i];
-        s_spx[i] = prep_px[cs + i];
-        s_nq[i] = noise_query[i];
-    }
-    for (int i = lane; i <= cs; i += 64) s_psi[i] = table_psi[i];
-    const size_t v = size_t(blockIdx.x) * 64 + lane;
-    // lanes past the end read 0 (num_voxels x element size is below kNarrowMaxBytes: nothing wraps)
-    const uint32_t byte_offset = uint32_t(v) * kElement, bytes = uint32_t(num_voxels) * kElement;
-    bool is_nan = false;
-#pragma unroll 8
-    for (int e = 0; e < cs; e++) {
-        const float y = narrow_code_value<FMT>(load_code_nt<FMT>(members[e], bytes, byte_offset));
-        if constexpr (FMT == CRF_MEMBER_F16) is_nan |= (y != y);  // the integer formats have no NaN
-        s_y[e * 64 + lane] = y;
-    }
-    __syncthreads();
-    const auto y_of = [&](int e) -> float { return s_y[e * 64 + lane]; };
-
-    const int last = cs - 1;  // the surplus points of the last sweep repeat it
-    int top = 1;
-    while (top * 2 <= cs) top *= 2;
-    const double factor = 1.0 / double(cs);
-    const double inf = __longlong_as_double(0x7FF0000000000000ll);
-    double sum_x = 0.0, sum_y = 0.0;
-
-#pragma unroll 1
-    for (int i0 = 0; i0 < cs; i0 += TI) {
-        double pxi[TI], pyi[TI], rx[TI], ry[TI];
-#pragma unroll
-        for (int t = 0; t < TI; t++) {
-            const int ii = (i0 + t < cs) ? i0 + t : last;
-            pxi[t] = s_px[ii];
-            pyi[t] = double(y_of(ii)) + s_nq[ii];
-        }
-        const int i1 = (i0 + TI < cs) ? i0 + TI : cs;
-        // ---- pass A: Chebyshev distance to the k-th neighbour (mi_kraskov_kernel)
-        double dk[TI];
-        double best[TI][K];
-#pragma unroll
-        for (int t = 0; t < TI; t++)
-#pragma unroll
-            for (int q = 0; q < K; q++) best[t][q] = inf;
-        auto visit = [&](int j, bool may_be_self) {
-            const double pxj = s_px[j];
-            const double pyj = double(y_of(j)) + s_nq[j];
-#pragma unroll
-            for (int t = 0; t < TI; t++) {
-                double d = chebyshev_f64(pxi[t] - pxj, pyi[t] - pyj);
-                if (may_be_self) d = (j == i0 + t) ? inf : d;
-#pragma unroll
-                for (int q = 0; q < K; q++) {
-                    const double lo = min_f64(best[t][q], d);
-                    if (q + 1 < K) d = max_f64(best[t][q], d);
-                    best[t][q] = lo;
-                }
-            }
-        };
-        if constexpr (DXT) {
-            const double* dx_col = prep_px + dxt_offset(cs) + i0;
-            const int dxt_cols = (cs + 7) / 8 * 8;
-#pragma unroll 2
-            for (int j = 0; j < cs; j++) {
-                const double pyj = double(y_of(j)) + s_nq[j];
-                const double* dx_row = dx_col + size_t(j) * size_t(dxt_cols);
-#pragma unroll
-                for (int t = 0; t < TI; t++) {
-                    double d = chebyshev_f64_sx(pyi[t] - pyj, dx_row[t]);
-#pragma unroll
-                    for (int q = 0; q < K; q++) {
-                        const double lo = min_f64(best[t][q], d);
-                        if (q + 1 < K) d = max_f64(best[t][q], d);
-                        best[t][q] = lo;
-                    }
-                }
-            }
-        } else {
-#pragma unroll 2
-            for (int j = 0; j < i0; j++) visit(j, false);
-#pragma unroll 1
-            for (int j = i0; j < i1; j++) visit(j, true);
-#pragma unroll 2
-            for (int j = i1; j < cs; j++) visit(j, false);
-        }
-#pragma unroll
-        for (int t = 0; t < TI; t++) dk[t] = best[t][K - 1];
-        // ---- search radii
-        if (estimator == 1) {
-#pragma unroll
-            for (int t = 0; t < TI; t++) rx[t] = ry[t] = dk[t] - kCountSlack;
-        } else {
-            double ex[TI], ey[TI];
-#pragma unroll
-            for (int t = 0; t < TI; t++) ex[t] = ey[t] = 0.0;
-#pragma unroll 2
-            for (int j = 0; j < cs; j++) {
-                const double pxj = s_px[j];
-                const double pyj = double(y_of(j)) + s_nq[j];
-#pragma unroll
-                for (int t = 0; t < TI; t++) {
-                    const double ax = fabs(pxi[t] - pxj), ay = fabs(pyi[t] - pyj);
-                    const bool in = fmax(ax, ay) <= dk[t];
-                    ex[t] = in ? fmax(ex[t], ax) : ex[t];
-                    ey[t] = in ? fmax(ey[t], ay) : ey[t];
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < TI; t++) {
-                rx[t] = ex[t] + kCountSlack;
-                ry[t] = ey[t] + kCountSlack;
-            }
-        }
-        // ---- pass C: marginal counts
-        double loy[TI], hiy[TI];
-        int cx[TI], cy[TI];
-        {
-            double bound[TI];
-            int less[TI];
-#pragma unroll
-            for (int t = 0; t < TI; t++) bound[t] = pxi[t] + rx[t];
-            count_less_batch<TI>(s_spx, cs, top, bound, cx);
-#pragma unroll
-            for (int t = 0; t < TI; t++) bound[t] = pxi[t] - rx[t];
-            count_less_batch<TI>(s_spx, cs, top, bound, less);
-#pragma unroll
-            for (int t = 0; t < TI; t++) cx[t] -= less[t];
-        }
-#pragma unroll
-        for (int t = 0; t < TI; t++) {
-            loy[t] = pyi[t] - ry[t];
-            hiy[t] = pyi[t] + ry[t];
-            cy[t] = 0;
-        }
-#pragma unroll 2
-        for (int j = 0; j < cs; j++) {
-            const double pyj = double(y_of(j)) + s_nq[j];
-#pragma unroll
-            for (int t = 0; t < TI; t++) cy[t] += (pyj >= loy[t] && pyj < hiy[t]) ? 1 : 0;
-        }
-#pragma unroll
-        for (int t = 0; t < TI; t++) {
-            if (i0 + t < cs) {
-                int nx = cx[t] > 1 ? cx[t] : 1;
-                int ny = cy[t] > 1 ? cy[t] : 1;
-                if (estimator != 1) {
-                    nx -= 1;  // psi(n - 1), psi(0) = NaN (pole)
-                    ny -= 1;
-                }
-                sum_x += factor * s_psi[nx];
-                sum_y += factor * s_psi[ny];
-            }
-        }
-    }
-    const double d = s_psi[cs];
-    const double mi = -sum_x - sum_y + c_term + d;
-    float res = float(mi);
-    res = (res < 0.0f) ? 0.0f : res;
-    if (to_cc) res = mi_to_cc(res);
-    if (is_nan) res = __uint_as_float(0x7FC00000u);
-    if (v < num_voxels) store_result_nt(out + v, res);
 }
 
 // kraskov_direct_kernel (field mode, the four waves of a block sharing a voxel tile) on narrow members.  The block always
@@ -464,8 +287,7 @@ __global__ __launch_bounds__(256, direct_min_waves(K, TI, false)) void kraskov_d
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-using NarrowKernel = void (*)(const void* const*, const double*, const double*, const double*, float*, size_t, int, int,
-                              int, int, double);
+using NarrowKernel = KraskovColumnKernel;  // the tile-free kernel takes the column kernel's arguments
 
 // Where the values are parked, by measurement (profiles/narrow_kraskov_ab.md).  The LDS column: floats (codes cost 1-3 %
 // at k = 1 and 3 and gained 6 % only at k = 2; that form is not kept).  The tile of the tile-free kernel: floats up to 64
@@ -473,18 +295,8 @@ using NarrowKernel = void (*)(const void* const*, const double*, const double*, 
 // codes -- and codes above, where a tile of floats costs occupancy (11-25 % slower than the fp32 kernel at 80..128 members).
 constexpr int kFloatTileMaxMembers = 64;
 
-// Only what kraskov_narrow_plan routes is built.  Column: uint8 with K = 2, 3 at 33..48 members (the plan takes 16
-// points per sweep only above 56).  Tile-free: K = 2, 3, 4 and 8 (K = 1 is routed nowhere).
-NarrowKernel column_narrow_kernel(const KraskovPlan& p) {
-    constexpr int FMT = CRF_MEMBER_U8;
-    if (p.TI != 8) return nullptr;
-    switch (p.K) {
-        case 2: return p.dxt ? mi_kraskov_narrow_kernel<FMT, 2, 8, true> : mi_kraskov_narrow_kernel<FMT, 2, 8>;
-        case 3: return p.dxt ? mi_kraskov_narrow_kernel<FMT, 3, 8, true> : mi_kraskov_narrow_kernel<FMT, 3, 8>;
-        default: return nullptr;
-    }
-}
-
+// Only what kraskov_narrow_plan routes is built.  Tile-free: K = 2, 3, 4 and 8 (K = 1 is routed nowhere).  (Column:
+// kraskov_column_narrow_kernel, kernels_kraskov.hip.)
 template <int FMT, int PARK, int K>
 NarrowKernel direct_narrow_table_kernel(const KraskovPlan& p) {
     return p.TI == 4 ? kraskov_direct_narrow_kernel<FMT, PARK, K, 4, true> : kraskov_direct_narrow_kernel<FMT, PARK, K, 8, true>;
@@ -524,8 +336,8 @@ hipError_t launch_narrow(const KraskovPlan& p, const void* const* d_narrow, int 
     size_t lds = 0;
     unsigned blocks = 0, threads = 0;
     if (p.family == KraskovFamily::Column) {
-        if constexpr (FMT == CRF_MEMBER_U8) kernel = column_narrow_kernel(p);
-        lds = size_t(4 * cs + 1 + ((cs + 1) & 1)) * sizeof(double) + size_t(cs) * 64 * sizeof(float);
+        kernel = kraskov_column_narrow_kernel(FMT, p);
+        lds = kraskov_column_lds_bytes(cs);
         blocks = unsigned(tiles);
         threads = 64;
     } else {

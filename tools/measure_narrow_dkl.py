@@ -32,7 +32,7 @@ def default_k(cs):
 
 
 def instantiation(cs, kind):
-    """The kernel instantiation a call runs (launch_dkl_family): the padded network size, or the counting sort."""
+    """The kernel instantiation a call runs (launch_dkl_format, kernels_dkl.hip): the padded network size, or the counting sort."""
     networks = cs <= (96 if kind == "binned" else 128)
     return f"N = {(cs + 15) // 16 * 16}" if networks else "counting sort"
 
