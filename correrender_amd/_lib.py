@@ -91,6 +91,10 @@ SYMBOLS = {
     "crf_rank_values_device": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, _VOIDP, C.POINTER(C.c_ulonglong)]),
     "crf_field_rank_similarity": (C.c_int, [_VOIDP, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)]),
     "crf_rank_scratch_bytes": (C.c_size_t, [_VOIDP]),
+    "crf_kendall_values_device": (C.c_int, [_VOIDP, _VOIDP, _VOIDP, C.c_size_t, C.POINTER(C.c_float),
+                                            C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong)]),
+    "crf_field_kendall_similarity": (C.c_int, [_VOIDP, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_longlong),
+                                               C.POINTER(C.c_ulonglong)]),
     "crf_max_mutual_information_kraskov": (C.c_double, [C.c_int, C.c_int]),
     "crf_tiled_element_count": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "crf_tile_field_device": (C.c_int, [_VOIDP, _VOIDP, _VOIDP, _VOIDP]),

@@ -1719,6 +1719,76 @@ int crf_field_rank_similarity(crf_context* c, int measure, int member, float* ou
     return CRF_OK;
 }
 
+// ---- Kendall's tau-b over all samples: two sorts and an inversion count ------------------------------------------------------
+namespace {
+// the tail shared by the two entry points: the launcher's integers to the value and the caller's outputs
+void kendall_outputs(unsigned long long kept, const long long device_counts[3], float* out_value, long long* out_counts,
+                     unsigned long long* out_kept) {
+    *out_value = crf::similarity_kendall_from_counts(int64_t(kept), device_counts[0], device_counts[1], device_counts[2], out_counts);
+    if (out_kept) *out_kept = kept;
+}
+}  // namespace
+
+int crf_kendall_values_device(crf_context* c, const void* device_x, const void* device_y, size_t count, float* out_value,
+                              long long* out_counts, unsigned long long* out_kept) {
+    if (!c) return CRF_ERR_ARGUMENT;
+    if (!out_value) return fail(c, CRF_ERR_ARGUMENT, "null output");
+    const long long none[3] = {0, 0, 0};
+    if (count == 0) {
+        kendall_outputs(0, none, out_value, out_counts, out_kept);  // 0 / 0
+        return CRF_OK;
+    }
+    if (!device_x || !device_y) return fail(c, CRF_ERR_ARGUMENT, "null argument");
+    if (count > size_t(0x7FFFFFFF))
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%zu values: the sort carries 32-bit payloads (at most 2147483647)", count));
+    if (int r = bind_device(c)) return r;
+    if (int r = ensure_rank_scratch(c, crf::kendall_scratch_bytes(count))) return r;
+    TimedLaunch launch(c);
+    unsigned long long kept = 0;
+    long long counts[3] = {0, 0, 0};
+    if (int r = launch.finish(crf::launch_kendall_values(static_cast<const float*>(device_x), static_cast<const float*>(device_y),
+                                                         count, c->grid.rank_scratch.get(), c->stream, launch.e0, launch.e1,
+                                                         &kept, counts, &launch.info)))
+        return r;
+    kendall_outputs(kept, counts, out_value, out_counts, out_kept);
+    return CRF_OK;
+}
+
+// computeFieldSimilarity<double> with CRF_KENDALL (Similarity.cpp:134-143) on two resident fields.  An entry point of its
+// own: crf_field_similarity and crf_field_rank_similarity keep refusing Kendall.
+int crf_field_kendall_similarity(crf_context* c, int member, float* out_value, long long* out_counts,
+                                 unsigned long long* out_samples) {
+    if (int r = check_ready(c)) return r;
+    if (!out_value) return fail(c, CRF_ERR_ARGUMENT, "null output");
+    if (!c->grid.has_secondary())
+        return fail(c, CRF_ERR_STATE, "crf_field_kendall_similarity needs secondary members (crf_upload_secondary_members)");
+    if (member < -1 || member >= c->cs)
+        return fail(c, CRF_ERR_ARGUMENT, fmt("member %d outside [-1, %d)", member, c->cs));
+    if (c->windowed)
+        return fail(c, CRF_ERR_UNSUPPORTED, "crf_field_kendall_similarity does not evaluate windowed grids (member volumes of 4 GiB or more)");
+    const int members = member < 0 ? c->cs : 1;
+    if (size_t(members) * c->alloc_voxels > size_t(0x7FFFFFFF))
+        return fail(c, CRF_ERR_UNSUPPORTED, fmt("%zu samples: the reference counts the samples of a field similarity in an int "
+                                                "(at most 2147483647)", size_t(members) * c->alloc_voxels));
+    if (int r = bind_device(c)) return r;
+    hipStream_t s = c->stream;
+    if (int r = ensure_wide(c, s)) return r;
+    if (int r = ensure_secondary_wide(c, s)) return r;
+    if (int r = ensure_rank_scratch(c, crf::kendall_scratch_bytes(size_t(members) * c->alloc_voxels))) return r;
+    const crf_grid_state& g = c->grid;
+    const int first = member < 0 ? 0 : member;
+    crf::SimilarityJob job{c->view.members + first, c->view.secondary + first, members, c->alloc_voxels,
+                           g.members.vpt == 4 && g.secondary.vpt == 4, nullptr};
+    TimedLaunch launch(c);
+    unsigned long long kept = 0;
+    long long counts[3] = {0, 0, 0};
+    if (int r = launch.finish(crf::launch_kendall_similarity(job, g.rank_scratch.get(), s, launch.e0, launch.e1, &kept, counts,
+                                                             &launch.info)))
+        return r;
+    kendall_outputs(kept, counts, out_value, out_counts, out_samples);
+    return CRF_OK;
+}
+
 // ---- helpers, instrumentation, synthetic data -------------------------------------------------------------------------
 double crf_max_mutual_information_kraskov(int k, int cs) {
     if (k < 1 || cs < 1) return std::numeric_limits<double>::quiet_NaN();

@@ -71,9 +71,10 @@ struct crf_grid_state {
     // [0]: every launch on the context's stream or a caller's; [1]: the ranges of a host-output evaluation that run on
     // stream2.  Lazily; sized before the first launch of an evaluation, never between its ranges (api.cpp: ensure_todo).
     crf_scratch scratch[2];
-    // the device-wide sort of crf_rank_values_device / crf_field_rank_similarity (kernels_rank_similarity.hip): keys,
-    // payloads, tables and rank arrays, grown on demand (api.cpp: ensure_rank_scratch).  Not part of `scratch`: it is
-    // sized by the sample count, tens of GiB for a large field, and only these two calls use it.
+    // the device-wide sort of crf_rank_values_device / crf_field_rank_similarity (kernels_rank_similarity.hip) and of the
+    // two Kendall calls (kernels_kendall_similarity.hip): keys, payloads, tables and rank arrays, grown on demand (api.cpp:
+    // ensure_rank_scratch).  Not part of `scratch`: it is sized by the sample count, tens of GiB for a large field, and
+    // only these four calls use it.
     crf::DeviceBuffer<unsigned char> rank_scratch;
     // host-output evaluations (crf_compute): the grid in up to kMaxHostChunks voxel ranges, one member-pointer table per
     // range; the per-voxel kernel of a range stores into the pinned, device-mapped staging buffer and a pool of host

@@ -410,6 +410,22 @@ size_t rank_similarity_scratch_bytes(int members, size_t num_voxels);
 hipError_t launch_rank_similarity(const SimilarityJob& job, unsigned char* scratch, hipStream_t s, hipEvent_t ev_begin,
                                   hipEvent_t ev_end, LaunchInfo* info);
 
+// ---- kernels_kendall_similarity.hip: Kendall's tau-b over all samples ---------------------------------------------------------
+// The integers of computeKendall<int64_t> (Correlation.cpp:423-455) over the pairs (x[i], y[i]) without a NaN: *kept = n,
+// counts = {n1, n2, S} (ties of x, ties of y, strict inversions of y in the order of x, then y); crf_similarity_tail.h makes
+// the value of them.  Two sorts by the device-wide radix sort, then a tile kernel and merge levels that count inversions.
+// count in [1, 2^31 - 1]; d_x and d_y are only read and may be one array.  scratch: kendall_scratch_bytes(count) of device
+// memory, 256-byte aligned.  SYNCHRONISES the stream (the digit histograms, then the counts): everything is final on
+// return.  One event pair around all launches.
+size_t kendall_scratch_bytes(size_t count);
+hipError_t launch_kendall_values(const float* d_x, const float* d_y, size_t count, unsigned char* scratch, hipStream_t s,
+                                 hipEvent_t ev_begin, hipEvent_t ev_end, unsigned long long* kept, long long counts[3],
+                                 LaunchInfo* info);
+// The same over the samples of a SimilarityJob (job.workspace is not used); scratch: kendall_scratch_bytes(members x
+// num_voxels).
+hipError_t launch_kendall_similarity(const SimilarityJob& job, unsigned char* scratch, hipStream_t s, hipEvent_t ev_begin,
+                                     hipEvent_t ev_end, unsigned long long* kept, long long counts[3], LaunchInfo* info);
+
 // ---- two vectors per item: the symmetric field mode and pair requests --------------------------------------------------
 // One evaluation of a measure between two member vectors per item.  Field mode (requests == nullptr): item v is voxel
 // pair (v, v), X = members_x[.][v] (the primary field), Y = members_y[.][v] (the secondary field).  Request mode: item r

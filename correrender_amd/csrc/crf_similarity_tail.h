@@ -1,6 +1,7 @@
 // crf_similarity_tail.h -- the host half of crf_field_similarity's binned measures: from the joint histogram's integer
-// counts to the mutual information.  Plain C++, no HIP: api.cpp calls it on the counts similarity_histogram_kernel
-// leaves, tests/native/similarity_tail.cpp runs it without a GPU.
+// counts to the mutual information; and of the Kendall calls: from four integers to tau-b.  Plain C++, no HIP: api.cpp
+// calls it on the counts similarity_histogram_kernel and kernels_kendall_similarity.hip leave,
+// tests/native/similarity_tail.cpp and tests/native/kendall_tail.cpp run it without a GPU.
 //
 // The reference (computeMutualInformationBinned<double>, MutualInformation.cpp:45-143) adds 1.0 per sample into an fp64
 // histogram -- exact integers, so the histogram does not depend on the order the samples arrive in -- and everything
@@ -51,6 +52,22 @@ inline float similarity_mi_from_counts(const uint64_t* counts, int num_bins, uin
         if (p_xy > epsilon_2d) mi += p_xy * std::log(p_xy);
     }
     return float(mi);
+}
+
+// Kendall's tau-b from its integers, computeKendall<int64_t> (Correlation.cpp:439-453) verbatim: n pairs, n1 and n2 the
+// tie sums of x and of y (joint ties n3 stay 0, as there), S the strict inversions.  Exact integers, three IEEE double
+// operations and a cast; no special cases: no pair or one gives 0 / 0 = NaN, a constant side NaN or +-inf.  counts (may be
+// null) receives n0, n1, n2, S.
+inline float similarity_kendall_from_counts(int64_t n, int64_t n1, int64_t n2, int64_t s, long long* counts) {
+    const int64_t n0 = (n * (n - 1)) / 2;
+    const int64_t numerator = n0 - n1 - n2 - 2 * s;
+    // volatile: the division runs on the machine even where the compiler knows its operands (no pair: 0 / 0).  The
+    // reference's is a run-time division, and the x86-64 instruction gives the NaN with the sign bit set where a compiler
+    // that folds 0.0 / 0.0 gives the one without.
+    volatile double dividend = double(numerator);
+    volatile double denominator = std::sqrt(double(n0 - n1)) * std::sqrt(double(n0 - n2));
+    if (counts) counts[0] = n0, counts[1] = n1, counts[2] = n2, counts[3] = s;
+    return float(dividend / denominator);
 }
 
 // sqrt(1 - exp(-2 MI)) in fp32 with the host's expf (Similarity.cpp:165-167; on the device: crf_mi_device.h, mi_to_cc)

@@ -40,6 +40,9 @@
 //     samples differently from call to call and with them the fp64 sums (the value must be reproducible bit for bit); a
 //     counted compaction costs a second read of both fields.  Masking needs neither, nor the two compacted arrays.
 //   * The first scatter pass takes the identity as payload instead of reading one.
+//
+// The sort proper (sort_pairs), the run carries and the masking are also what kernels_kendall_similarity.hip starts from:
+// crf_rank_sort.h declares them and holds the device helpers both files use.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,28 +51,18 @@
 #include <vector>
 
 #include "crf_internal.h"
+#include "crf_rank_sort.h"
 #include "crf_similarity_chunks.h"
 
 namespace crf {
 namespace {
 
 using namespace chunks;
+using namespace ranksort;  // the constants, sort_key, head_bits, run_bounds, SortLayout (crf_rank_sort.h)
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxTileKeys = 4096;                 // 16 keys per thread; key and payload staged in 32 KiB of LDS
 constexpr int kMaxRounds = kMaxTileKeys / kThreads;
-constexpr int kMaxSortBlocks = 1024;               // rows of the [block][digit] table
 constexpr int kCarryThreads = 1024;
-constexpr uint32_t kNanKey = 0xFFFFFFFFu;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr int kMaskThreads = 256;
-
-__device__ __forceinline__ uint32_t sort_key(float v) {
-    if (v != v) return kNanKey;
-    const uint32_t u = __float_as_uint(v == 0.0f ? 0.0f : v);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
 
 // the keys [first, last) of block b: whole tiles, in index order over the blocks
 __device__ __forceinline__ void block_share(uint32_t n, uint32_t tile_keys, uint32_t tiles_per_block, uint32_t* first,
@@ -272,17 +265,6 @@ __global__ __launch_bounds__(kThreads) void similarity_rank_sort_kernel(const ui
     }
 }
 
-// the head bits of the 64 positions a wave looks at: bit l set where position tile + p is the first of a run
-__device__ __forceinline__ unsigned long long head_bits(const uint32_t* __restrict__ keys, uint32_t tile, uint32_t p,
-                                                        uint32_t tile_len) {
-    bool head = false;
-    if (p < tile_len) {
-        const uint32_t i = tile + p;
-        head = i == 0u || keys[i] != keys[i - 1u];
-    }
-    return __ballot(head);
-}
-
 // first_head[t]: position of the first head of tile t, kNone if it has none;  last_head[t]: 1 + position of the last, 0
 __global__ __launch_bounds__(kThreads) void rank_heads_kernel(const uint32_t* __restrict__ keys, uint32_t n,
                                                               uint32_t tile_keys, uint32_t tiles,
@@ -348,49 +330,19 @@ __global__ __launch_bounds__(kThreads) void rank_assign_kernel(const uint32_t* _
                                                                const uint32_t* __restrict__ head_after,
                                                                const uint32_t* __restrict__ head_before,
                                                                float* __restrict__ ranks) {
-    __shared__ unsigned long long heads[kMaxTileKeys / 64];  // word j: positions 64 j .. 64 j + 63 of the tile
-    __shared__ uint32_t word_before[kMaxTileKeys / 64];      // 1 + tile position of the last head in the words before j, 0
-    __shared__ uint32_t word_after[kMaxTileKeys / 64];       // tile position of the first head in the words after j, kNone
+    __shared__ RunWords words;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int rounds = int((tile_keys + kThreads - 1) / kThreads);
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const uint32_t tile = t * tile_keys;
         const uint32_t tile_len = min(tile_keys, n - tile);
-        for (int r = 0; r < rounds; r++) {
-            const uint32_t p0 = uint32_t(r * kThreads + w * 64);
-            const unsigned long long m = head_bits(keys, tile, p0 + uint32_t(lane), tile_len);
-            if (lane == 0) heads[p0 >> 6] = m;
-        }
-        __syncthreads();
-        if (w == 0) {  // one wave: at most 64 words
-            const int words = rounds * kWaves;
-            const unsigned long long m = lane < words ? heads[lane] : 0ull;
-            uint32_t last = m != 0ull ? uint32_t(lane * 64 + 64 - __clzll((long long)m)) : 0u;
-            uint32_t first = m != 0ull ? uint32_t(lane * 64 + __ffsll((long long)m) - 1) : kNone;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {  // inclusive: max from the left, min from the right
-                const uint32_t l = __shfl_up(last, off), f = __shfl_down(first, off);
-                if (lane >= off) last = max(last, l);
-                if (lane + off < 64) first = min(first, f);
-            }
-            const uint32_t l = __shfl_up(last, 1), f = __shfl_down(first, 1);
-            word_before[lane] = lane > 0 ? l : 0u;
-            word_after[lane] = lane < 63 ? f : kNone;
-        }
-        __syncthreads();
+        tile_head_words(keys, tile, tile_len, rounds, words);
         const uint32_t carry_start = head_before[t], carry_end = head_after[t];
         for (int r = 0; r < rounds; r++) {
             const uint32_t p = uint32_t(r * kThreads + w * 64 + lane);
             if (p >= tile_len) continue;
-            const uint32_t j = p >> 6;
-            const unsigned long long m = heads[j];
-            const unsigned long long upto = m & (~0ull >> (63 - lane));                  // heads at or before p
-            const unsigned long long past = lane == 63 ? 0ull : m & (~0ull << (lane + 1));  // heads after p
             uint32_t s, e;
-            if (upto != 0ull) s = tile + j * 64u + uint32_t(63 - __clzll((long long)upto));
-            else s = word_before[j] != 0u ? tile + word_before[j] - 1u : carry_start;
-            if (past != 0ull) e = tile + j * 64u + uint32_t(__ffsll((long long)past) - 1);
-            else e = word_after[j] != kNone ? tile + word_after[j] : carry_end;
+            run_bounds(words, tile, p, carry_start, carry_end, &s, &e);
             const uint32_t i = tile + p;
             // one fp32 addition of two rounded terms (the product by 0.5 is exact)
             const float rank = keys[i] == kNanKey ? std::numeric_limits<float>::quiet_NaN()
@@ -425,37 +377,63 @@ __global__ __launch_bounds__(kMaskThreads) void rank_mask_pairs_kernel(Samples s
     }
 }
 
-// CRF_RANK_TILE_KEYS (tests): fewer keys per tile, so that a few thousand values span many tiles and blocks
+}  // namespace
+
+namespace ranksort {
+
 uint32_t tile_keys_setting() {
     const char* v = getenv("CRF_RANK_TILE_KEYS");
     const int t = (v && *v) ? atoi(v) : 0;
     return t > 0 ? uint32_t(std::min(t, kMaxTileKeys)) : uint32_t(kMaxTileKeys);
 }
 
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
-// scratch layout of a sort of n keys
-struct SortLayout {
-    size_t keys[2], payload[2], hist, nans, table, first_head, last_head, bytes;
-    explicit SortLayout(size_t n) {
-        size_t at = 0;
-        auto take = [&](size_t b) {
-            const size_t o = at;
-            at += align256(b);
-            return o;
-        };
-        for (int i = 0; i < 2; i++) keys[i] = take(n * 4), payload[i] = take(n * 4);
-        hist = take(4 * 256 * 4);
-        nans = take(4);
-        table = take(size_t(kMaxSortBlocks) * 256 * 4);
-        const size_t heads = (n + tile_keys_setting() - 1) / tile_keys_setting();
-        first_head = take(heads * 4);
-        last_head = take(heads * 4);
-        bytes = at;
+int sort_pairs(uint32_t* const keys[2], uint32_t* const payload[2], int cur, uint32_t n, const uint32_t* host_hist,
+               const uint32_t* d_hist, uint32_t* d_table, bool identity, int wanted_blocks, hipStream_t s, int* passes) {
+    const uint32_t tile_keys = tile_keys_setting();
+    const uint32_t tiles = (n + tile_keys - 1) / tile_keys;
+    const uint32_t sort_blocks = grid_blocks(tiles, wanted_blocks);
+    const uint32_t tiles_per_block = (tiles + sort_blocks - 1) / sort_blocks;
+    const uint32_t used_blocks = (tiles + tiles_per_block - 1) / tiles_per_block;  // the rest would own nothing
+    int run = 0;
+    for (int d = 0; d < 4; d++) {
+        bool one_bin = false;
+        for (int b = 0; b < 256; b++) one_bin = one_bin || host_hist[d * 256 + b] == n;
+        if (one_bin) continue;  // every key has this digit: the pass would be the identity
+        const int shift = 8 * d;
+        hipLaunchKernelGGL(rank_count_kernel, dim3(used_blocks), dim3(kThreads), 0, s, keys[cur], n, shift, tile_keys,
+                           tiles_per_block, d_table);
+        hipLaunchKernelGGL(rank_scan_kernel, dim3(256), dim3(kThreads), 0, s, d_table, used_blocks, d_hist + d * 256);
+        hipLaunchKernelGGL(similarity_rank_sort_kernel, dim3(used_blocks), dim3(kThreads), 0, s, keys[cur], payload[cur], n, shift,
+                           int(identity && run == 0), tile_keys, tiles_per_block, d_table, keys[cur ^ 1], payload[cur ^ 1]);
+        cur ^= 1;
+        run++;
     }
-};
+    if (passes) *passes = run;
+    return cur;
+}
 
-}  // namespace
+void launch_run_carries(const uint32_t* keys, uint32_t n, int wanted_blocks, uint32_t* head_after, uint32_t* head_before,
+                        hipStream_t s) {
+    const uint32_t tile_keys = tile_keys_setting();
+    const uint32_t tiles = (n + tile_keys - 1) / tile_keys;
+    hipLaunchKernelGGL(rank_heads_kernel, dim3(grid_blocks(tiles, wanted_blocks)), dim3(kThreads), 0, s, keys, n, tile_keys,
+                       tiles, head_after, head_before);
+    hipLaunchKernelGGL(rank_carry_kernel, dim3(1), dim3(kCarryThreads), 0, s, head_after, head_before, tiles, n);
+}
+
+hipError_t launch_mask_pairs(const SimilarityJob& job, float* out_x, float* out_y, hipStream_t s) {
+    int cus = 0;
+    if (hipError_t e = compute_units(&cus); e != hipSuccess) return e;
+    const Samples smp = make_samples(job, kMaskThreads);
+    const uint32_t blocks = grid_blocks(smp.chunks, std::min(4 * cus, kMaxSortBlocks));
+    if (job.vec16)
+        hipLaunchKernelGGL((rank_mask_pairs_kernel<true>), dim3(blocks), dim3(kMaskThreads), 0, s, smp, out_x, out_y);
+    else
+        hipLaunchKernelGGL((rank_mask_pairs_kernel<false>), dim3(blocks), dim3(kMaskThreads), 0, s, smp, out_x, out_y);
+    return hipGetLastError();
+}
+
+}  // namespace ranksort
 
 size_t rank_sort_scratch_bytes(size_t count) { return SortLayout(count).bytes; }
 
@@ -496,29 +474,11 @@ hipError_t launch_rank_values(const float* d_values, size_t count, float* d_rank
     if (hipError_t e = hipStreamSynchronize(s); e != hipSuccess) return e;
     if (ranked) *ranked = count - host[4 * 256];
 
-    const uint32_t sort_blocks = grid_blocks(tiles, wanted);
-    const uint32_t tiles_per_block = (tiles + sort_blocks - 1) / sort_blocks;
-    const uint32_t used_blocks = (tiles + tiles_per_block - 1) / tiles_per_block;  // the rest would own nothing
-    int cur = 0, identity = 1;
-    for (int d = 0; d < 4; d++) {
-        bool one_bin = false;
-        for (int b = 0; b < 256; b++) one_bin = one_bin || host[d * 256 + b] == n;
-        if (one_bin) continue;  // every key has this digit: the pass would be the identity
-        const int shift = 8 * d;
-        hipLaunchKernelGGL(rank_count_kernel, dim3(used_blocks), dim3(kThreads), 0, s, keys[cur], n, shift, tile_keys,
-                           tiles_per_block, u32(lay.table));
-        hipLaunchKernelGGL(rank_scan_kernel, dim3(256), dim3(kThreads), 0, s, u32(lay.table), used_blocks,
-                           u32(lay.hist) + d * 256);
-        hipLaunchKernelGGL(similarity_rank_sort_kernel, dim3(used_blocks), dim3(kThreads), 0, s, keys[cur], payload[cur], n, shift,
-                           identity, tile_keys, tiles_per_block, u32(lay.table), keys[cur ^ 1],
-                           payload[cur ^ 1]);
-        cur ^= 1;
-        identity = 0;
-    }
+    int passes = 0;
+    const int cur = sort_pairs(keys, payload, 0, n, host, u32(lay.hist), u32(lay.table), true, wanted, s, &passes);
+    const int identity = passes == 0;
     const uint32_t rank_blocks = grid_blocks(tiles, wanted);
-    hipLaunchKernelGGL(rank_heads_kernel, dim3(rank_blocks), dim3(kThreads), 0, s, keys[cur], n, tile_keys, tiles,
-                       u32(lay.first_head), u32(lay.last_head));
-    hipLaunchKernelGGL(rank_carry_kernel, dim3(1), dim3(kCarryThreads), 0, s, u32(lay.first_head), u32(lay.last_head), tiles, n);
+    launch_run_carries(keys[cur], n, wanted, u32(lay.first_head), u32(lay.last_head), s);
     hipLaunchKernelGGL(rank_assign_kernel, dim3(rank_blocks), dim3(kThreads), 0, s, keys[cur], payload[cur], identity, n,
                        tile_keys, tiles, u32(lay.first_head), u32(lay.last_head), d_ranks);
     if (ev_end) (void)hipEventRecord(ev_end, s);
@@ -532,8 +492,6 @@ hipError_t launch_rank_similarity(const SimilarityJob& job, unsigned char* scrat
     if (job.members < 1 || job.num_voxels < 1 || job.num_voxels >= (size_t(1) << 30) || n > size_t(0x7FFFFFFF) ||
         !job.workspace || !scratch)
         return hipErrorInvalidValue;
-    int cus = 0;
-    if (hipError_t e = compute_units(&cus); e != hipSuccess) return e;
     const size_t sort_bytes = SortLayout(n).bytes;
     float* rank_x = reinterpret_cast<float*>(scratch + sort_bytes);
     float* rank_y = reinterpret_cast<float*>(scratch + sort_bytes + align256(n * 4));
@@ -550,12 +508,7 @@ hipError_t launch_rank_similarity(const SimilarityJob& job, unsigned char* scrat
     if (hipError_t e = hipMemcpyAsync(table_y, slices.data() + job.members, table_bytes, hipMemcpyHostToDevice, s); e != hipSuccess)
         return e;
     if (ev_begin) (void)hipEventRecord(ev_begin, s);
-    const Samples smp = make_samples(job, kMaskThreads);
-    const uint32_t blocks = grid_blocks(smp.chunks, std::min(4 * cus, kMaxSortBlocks));
-    if (job.vec16)
-        hipLaunchKernelGGL((rank_mask_pairs_kernel<true>), dim3(blocks), dim3(kMaskThreads), 0, s, smp, rank_x, rank_y);
-    else
-        hipLaunchKernelGGL((rank_mask_pairs_kernel<false>), dim3(blocks), dim3(kMaskThreads), 0, s, smp, rank_x, rank_y);
+    if (hipError_t e = launch_mask_pairs(job, rank_x, rank_y, s); e != hipSuccess) return e;
     // in place: the values are read once, into keys, before the first rank is stored
     if (hipError_t e = launch_rank_values(rank_x, n, rank_x, scratch, s, nullptr, nullptr, nullptr, nullptr); e != hipSuccess) return e;
     if (hipError_t e = launch_rank_values(rank_y, n, rank_y, scratch, s, nullptr, nullptr, nullptr, nullptr); e != hipSuccess) return e;

@@ -496,9 +496,43 @@ class CorrField:
                                                         C.byref(value), C.byref(samples)))
         return (value.value, int(samples.value)) if return_samples else value.value
 
+    def kendall_values(self, x, y, *, return_counts: bool = False):
+        """Kendall's tau-b of two contiguous float32 CUDA tensors of one size (they may be the same tensor; neither is
+        written), over the pairs without a NaN -- the reference's computeKendall<int64_t> (Correlation.cpp:423-455), bit for
+        bit: two device-wide sorts, then an inversion count by merging.  With `return_counts`: (value, pairs kept,
+        (n0, n1, n2, S)) -- the order field_kendall_similarity() returns them in; the integers are what the value is a
+        function of."""
+        import torch
+        for v in (x, y):
+            if v.dtype != torch.float32 or not v.is_cuda or not v.is_contiguous():
+                raise ValueError("kendall_values: contiguous float32 CUDA tensors are required")
+        if x.numel() != y.numel():
+            raise ValueError("kendall_values: x and y differ in size")
+        torch.cuda.current_stream(x.device).synchronize()        # the call runs on the context's own stream
+        value, counts, kept = C.c_float(), (C.c_longlong * 4)(), C.c_ulonglong()
+        self._check(self._lib.crf_kendall_values_device(self._ctx, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                        x.numel(), C.byref(value), counts, C.byref(kept)))
+        return (value.value, int(kept.value), tuple(int(v) for v in counts)) if return_counts else value.value
+
+    def field_kendall_similarity(self, *, member: Optional[int] = None, return_samples: bool = False,
+                                 return_counts: bool = False):
+        """computeFieldSimilarity<double> with Kendall (Similarity.cpp:134-143) between the primary field (x) and the
+        secondary field (y): tau-b as computeKendall<int64_t> forms it, over the samples field_similarity() takes, bit for
+        bit.  Returns the value; with `return_samples` and / or `return_counts` a tuple of the value, then the number of
+        pairs kept, then (n0, n1, n2, S)."""
+        value, counts, samples = C.c_float(), (C.c_longlong * 4)(), C.c_ulonglong()
+        self._check(self._lib.crf_field_kendall_similarity(self._ctx, -1 if member is None else int(member),
+                                                           C.byref(value), counts, C.byref(samples)))
+        out = (value.value,)
+        if return_samples:
+            out += (int(samples.value),)
+        if return_counts:
+            out += (tuple(int(v) for v in counts),)
+        return out if len(out) > 1 else out[0]
+
     def rank_scratch_bytes(self) -> int:
-        """Device memory the sort of rank_values() / field_rank_similarity() currently holds (0 before first use;
-        set_grid releases it)."""
+        """Device memory the sort of rank_values() / field_rank_similarity() / kendall_values() /
+        field_kendall_similarity() currently holds (0 before first use; set_grid releases it)."""
         return int(self._lib.crf_rank_scratch_bytes(self._ctx))
 
     def tiled_element_count(self) -> int:

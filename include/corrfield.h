@@ -131,7 +131,8 @@ int crf_abi_version(void);  /* 5: crf_group_compute_batch[_device], crf_member_m
                                   crf_last_member_format, crf_wide_copy_bytes, crf_window_count,
                                   crf_upload_secondary_members_format, crf_bind_secondary_members_device_format,
                                   crf_secondary_member_format, crf_secondary_wide_copy_bytes, crf_field_similarity,
-                                  crf_rank_values_device, crf_field_rank_similarity, crf_rank_scratch_bytes;
+                                  crf_rank_values_device, crf_field_rank_similarity, crf_rank_scratch_bytes,
+                                  crf_kendall_values_device, crf_field_kendall_similarity;
                                4: crf_group_* (several devices behind one caller thread), crf_set_kraskov_noise;
                                3: crf_params.reserved[0] became prepared_slot (same layout; 0 keeps the old meaning) */
 
@@ -456,8 +457,9 @@ int crf_compute_dkl_device(crf_context* ctx, int estimator, int num_bins, int k,
  *                      forms the product in fp64: bit-identical to the object code up to 46 340 samples, well defined beyond.
  *   CRF_BINNED_MI_CC   sqrt(1 - exp(-2 MI)) of that float (Similarity.cpp:165-167).
  *   CRF_SPEARMAN, CRF_KENDALL, CRF_MI_KRASKOV, CRF_KMI_CC: CRF_ERR_UNSUPPORTED -- they need a global sort or a k-nearest-
- *                      neighbour search over all N samples.  Spearman has an entry point of its own:
- *                      crf_field_rank_similarity below.
+ *                      neighbour search over all N samples.  Spearman and Kendall have entry points of their own:
+ *                      crf_field_rank_similarity and crf_field_kendall_similarity below.  Kraskov MI over all samples is
+ *                      not served.
  * Refusals (the context stays usable): no secondary members CRF_ERR_STATE; member outside [-1, cs) or num_bins outside
  * [1, 128] CRF_ERR_ARGUMENT; a windowed grid (crf_window_count > 1), or more than 2^31 - 1 candidate samples (the
  * reference counts samples in an int), CRF_ERR_UNSUPPORTED.  Members in a narrow format are read through their fp32
@@ -488,7 +490,8 @@ int crf_field_similarity(crf_context* ctx, int measure, int member, int num_bins
  *                  arrays by the moments path of crf_field_similarity: Sxy / (sqrt(Sxx) sqrt(Syy)) in fp64 with a fixed
  *                  order, cast to float; bitwise reproducible from call to call.  No pair kept: 0; one pair, or a constant
  *                  side: NaN.
- *   CRF_KENDALL    CRF_ERR_UNSUPPORTED: it needs an inversion count over all samples on top of the sort.
+ *   CRF_KENDALL    CRF_ERR_UNSUPPORTED: it needs an inversion count over all samples on top of the sort.  That is what
+ *                  crf_field_kendall_similarity (below) does; this call keeps its refusal.
  *   every other measure: CRF_ERR_ARGUMENT (crf_field_similarity serves Pearson and binned MI).
  * Refusals as for crf_field_similarity (the context stays usable): no secondary members CRF_ERR_STATE; member outside
  * [-1, cs) CRF_ERR_ARGUMENT; a windowed grid, or more than 2^31 - 1 candidate samples, CRF_ERR_UNSUPPORTED.  Narrow
@@ -507,6 +510,43 @@ int crf_rank_values_device(crf_context* ctx, const void* device_values, size_t c
 int crf_field_rank_similarity(crf_context* ctx, int measure, int member,
                               float* out_value, unsigned long long* out_samples /* may be NULL */);
 size_t crf_rank_scratch_bytes(const crf_context* ctx);
+
+/* ---- Kendall's tau-b over all samples: two sorts and an inversion count -----------------------------------------------------
+ * computeKendall<int64_t> (Correlation.cpp:423-455), which computeFieldSimilarity<double> calls for CRF_KENDALL
+ * (Similarity.cpp:134-143), bit for bit at every size.  Over the pairs (x_i, y_i) without a NaN on either side, n of them:
+ *   n0 = n (n - 1) / 2
+ *   n1 = the sum of m (m - 1) / 2 over the runs of m equal x;  n2 = the same over y.  Values compare as floats: -0 and +0
+ *        are equal, +-inf are ordinary values.  Joint ties stay 0, as in the reference -- which is why the value differs
+ *        from SciPy's tau-b on tied data.
+ *   S  = the strict inversions of the y sequence in the order of std::sort on pair<float, float>: x ascending, y ascending
+ *        among equal x; the pairs i < j of that order with y_j < y_i
+ *   value = float(double(n0 - n1 - n2 - 2 S) / (sqrt(double(n0 - n1)) * sqrt(double(n0 - n2))))
+ * evaluated as written on the host (crf_similarity_tail.h) from integers the device counts exactly
+ * (kernels_kendall_similarity.hip: the device-wide radix sort by y, then by x, a tile kernel and merge levels that count
+ * inversions; integer atomics only).  No tolerance is involved and the result is the same from call to call.  No special
+ * cases: no pair kept or one gives 0 / 0 = NaN, a constant side NaN or +-inf, as IEEE gives them.  out_counts (may be
+ * NULL) receives n0, n1, n2, S.
+ *
+ * crf_kendall_values_device: two fp32 device arrays of `count` values, count at most 2^31 - 1.  The inputs are only read
+ * and may be the same array.  count == 0: NaN, 0 kept, no device work.  *out_kept = n.  Synchronous on the context's own
+ * stream.
+ *
+ * crf_field_kendall_similarity: over the samples crf_field_similarity takes: every voxel of every member (member == -1) or
+ * of member `member`.  Refusals as for crf_field_rank_similarity, with the same codes (the context stays usable): no
+ * secondary members CRF_ERR_STATE; member outside [-1, cs) CRF_ERR_ARGUMENT; a windowed grid, or more than 2^31 - 1
+ * candidate samples, CRF_ERR_UNSUPPORTED.  Narrow members are read through their fp32 copies.  *out_samples = n.
+ *
+ * Both: crf_last_kernel_name reports similarity_kendall_merge_kernel; crf_set_profiling covers all launches of a call with
+ * one event pair.  Scratch is the sort's buffer (above: grown on demand, reported by crf_rank_scratch_bytes, released by
+ * crf_set_grid and crf_destroy): 16 bytes per value or candidate sample (the ping-pong of key and payload, which also
+ * holds the masked samples of the field call and the buffers of the merge levels: nothing is compacted), plus about
+ * 1 MiB of tables and less than count / 64 bytes (the heads of the tiles, the cuts of the merge chunks). */
+int crf_kendall_values_device(crf_context* ctx, const void* device_x, const void* device_y, size_t count,
+                              float* out_value, long long* out_counts /* 4: n0, n1, n2, S; may be NULL */,
+                              unsigned long long* out_kept /* may be NULL */);
+int crf_field_kendall_similarity(crf_context* ctx, int member, float* out_value,
+                                 long long* out_counts /* 4: n0, n1, n2, S; may be NULL */,
+                                 unsigned long long* out_samples /* may be NULL */);
 
 /* ---- result layout for the renderer -------------------------------------------------------------------------------- */
 /* The reference keeps device fields in 8x8x4 tiles (bufferTileSize, VolumeData.cpp:1581-1621; addressed by IDXS of
